@@ -31,6 +31,15 @@ The JSON line also carries:
                 duration vs 8 TB/s HBM; traffic = HBM bytes per launch from the
                 committed rocprofv3 PMC summary (profiles/integrate_pmc.json)
   cpu_baseline  the serial C++ oracle running the same pipeline on host cores
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the line: value, ms_per_step, the timed region's kernel ms
+and the integrate roofline from them.  Everything that takes a run of its own
+(profiled stage_ms frames, raycast work, host_input, extract, cpu_baseline and
+the C1 / C3 / C5 records, the N>1 `zslab` record) runs only with --full.
+
+--dump-outputs DIR writes what the last timed frame left for a caller (poses,
+the raycast maps, a seeded sample of volume columns) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -106,7 +115,78 @@ def parse():
     ap.add_argument("--c5-frames", type=int, default=10,
                     help="N=1, C2: timed frames of the C5 single-volume record (1280x720, 2048^3 @ 2 mm: the "
                          "N=1 point of the zslab curve; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: profiled stage_ms frames, raycast work, host_input, "
+                         "extract, cpu_baseline, the C1 / C3 / C5 records and (N>1) the zslab record; a plain "
+                         "run times the line's frames only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write the last frame's outputs (pose record, raycast vertex / "
+                         "normal maps, a seeded sample of volume columns) as DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+SIDE_RUNS = ("profile_frames", "cpu_frames", "host_frames", "c1_frames", "c3_frames", "c5_frames", "extract")
+
+
+def plain(a):
+    """Without --full only the line's frames run: every side measurement's
+    frame count is zeroed and the N>1 zslab record is off."""
+    if not a.full:
+        for k in SIDE_RUNS:
+            setattr(a, k, 0)
+        a.zslab = "none"
+    return a
+
+
+DUMP_LIMIT = 60 << 20  # bytes of all dumped arrays together
+DUMP_SEED = 20240607
+
+
+def fit_dump(arrays, limit=DUMP_LIMIT):
+    """Arrays (name -> float array, rows along axis 0) within `limit` bytes in
+    all: when they exceed it, every array above 1 MiB keeps a fixed, seeded
+    sample of its rows (sorted, so the order is the array's own)."""
+    total = sum(v.nbytes for v in arrays.values())
+    if total <= limit:
+        return arrays
+    small = sum(v.nbytes for v in arrays.values() if v.nbytes <= (1 << 20))
+    ratio = max(limit - small, 0) / (total - small)
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {}
+    for k, v in arrays.items():
+        if v.nbytes > (1 << 20):
+            keep = np.sort(rng.choice(v.shape[0], max(int(v.shape[0] * ratio), 1), replace=False))
+            v = v[keep]
+        out[k] = v
+    return out
+
+
+def dump_outputs(kf, path, n_cols=None):
+    """What the last timed frame left for a caller, as <path>/<name>.npy
+    (float32): the pose record up to it and the current camera pose, the raycast
+    vertex / normal maps of every pyramid level (the next frame's ICP target)
+    and tsdf / weight / colour of a seeded sample of the volume's (x, y) columns
+    over this context's slices.  Reads only; the frames that follow see the
+    same state."""
+    from kfx.abi import KFX_FRAME_PREV
+    X, Y, Z = kf.dims
+    arrays = {"pose_record": kf.pose_record.astype(np.float32),
+              "camera_pose": kf.getCurCameraPose().astype(np.float32)}
+    for l in range(int(kf.params.pyramid_height)):
+        _, v, n = kf.frame_maps(KFX_FRAME_PREV, l)
+        arrays[f"raycast_vertex_l{l}"] = v.reshape(-1, 3)
+        arrays[f"raycast_normal_l{l}"] = n.reshape(-1, 3)
+    rng = np.random.default_rng(DUMP_SEED)
+    n_cols = n_cols or max((1 << 20) // Z, 1)
+    cols = np.stack([rng.integers(0, X, n_cols), rng.integers(0, Y, n_cols)], axis=1).astype(np.int32)
+    t, w, c = kf.download_columns(cols)
+    arrays["volume_columns_xy"] = cols.astype(np.float32)
+    arrays["volume_tsdf"] = t.astype(np.float32)
+    arrays["volume_weight"] = w.astype(np.float32)
+    arrays["volume_rgb"] = c[..., :3].astype(np.float32).reshape(n_cols, -1)
+    os.makedirs(path, exist_ok=True)
+    for k, v in fit_dump(arrays).items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, np.float32))
 
 
 def intrinsics(w, h):
@@ -508,7 +588,7 @@ def single_record(a, name, intr, n, L, frames, D, local, traffic_path=None):
 
 
 def main():
-    a = parse()
+    a = plain(parse())
     # stdout carries only the JSON line: library banners (RCCL prints its
     # version there) and any other output go to stderr
     json_fd = os.dup(1)
@@ -700,6 +780,8 @@ def measure_main(a, name, intr, params, frames, D, rank, world, local, mode, icp
     kf, r = run_stream(a, intr, params, frames, D, local, slab=slab, icp_ar=icp_ar, gmode=graph_mode(a, name))
     elapsed, ktime, tracked, gmode = r["elapsed"], r["ktime"], r["tracked"], r["graph_mode"]
     ms_source = (f"timed region, {ktime['samples']} HIP-event-bracketed frames" if ktime else "profiled frames")
+    if a.dump_outputs and rank == 0:  # the last timed frame's outputs, before any further frame runs
+        dump_outputs(kf, a.dump_outputs)
 
     # per-stage device ms on further frames (profiled, eager; single volume)
     stages = {k: [] for k in ("preprocess", "icp", "integrate", "raycast", "total")}

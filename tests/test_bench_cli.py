@@ -96,6 +96,90 @@ def test_cli_defaults_pin_the_measured_configs(monkeypatch):
     assert b.CONFIGS["c5"] == (1280, 720, 2048, 4.096)
 
 
+def test_plain_run_times_only_the_line(monkeypatch):
+    """Without --full every side measurement is off (no profiled frames, CPU
+    baselines, host-input, extract, C1 / C3 / C5 or zslab records); --full
+    restores the defaults the records were measured with, and explicit counts
+    still apply under it."""
+    b = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = b.plain(b.parse())
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert [getattr(a, k) for k in b.SIDE_RUNS] == [0] * len(b.SIDE_RUNS) and a.zslab == "none"
+    assert a.sample_every == 8  # the timed region itself is measured as before
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--c5-frames", "0", "--dump-outputs", "d"])
+    a = b.plain(b.parse())
+    assert (a.full, a.dump_outputs, a.zslab) == (True, "d", "c5")
+    assert (a.profile_frames, a.cpu_frames, a.host_frames, a.c1_frames, a.c3_frames, a.c5_frames, a.extract) == (
+        20, 8, 200, 100, 20, 0, 1)
+
+
+class _DumpKF:
+    """The read-only accessors dump_outputs uses, with recognisable values."""
+    dims = (8, 8, 16)
+    params = types.SimpleNamespace(pyramid_height=2)
+
+    @property
+    def pose_record(self):
+        import numpy as np
+        return np.tile(np.eye(4, dtype=np.float32), (5, 1, 1))
+
+    def getCurCameraPose(self):
+        import numpy as np
+        return np.eye(4, dtype=np.float32)
+
+    def frame_maps(self, which, level):
+        import numpy as np
+        assert which == 1  # KFX_FRAME_PREV: the raycast maps
+        h, w = 4 >> level, 6 >> level
+        return None, np.full((h, w, 3), 1.0 + level, np.float32), np.full((h, w, 3), -1.0 - level, np.float32)
+
+    def download_columns(self, cols):
+        import numpy as np
+        assert cols.dtype == np.int32 and cols.min() >= 0 and cols.max() < 8
+        n = cols.shape[0]
+        z = np.arange(16, dtype=np.int16)
+        rgb = np.zeros((n, 16, 4), np.uint8)
+        rgb[..., :3] = (7, 8, 9)
+        return np.tile(z, (n, 1)), np.tile(z + 100, (n, 1)), rgb
+
+
+def test_dump_outputs_writes_float_arrays_of_the_last_frame(tmp_path, monkeypatch):
+    import numpy as np
+    b = load_bench()
+    abi = types.ModuleType("kfx.abi")
+    abi.KFX_FRAME_PREV = 1
+    monkeypatch.setitem(sys.modules, "kfx", types.ModuleType("kfx"))
+    monkeypatch.setitem(sys.modules, "kfx.abi", abi)
+    for d in ("a", "b"):  # two runs: the sampled columns are the same
+        b.dump_outputs(_DumpKF(), str(tmp_path / d), n_cols=5)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(n + ".npy" for n in (
+        "pose_record", "camera_pose", "raycast_vertex_l0", "raycast_normal_l0", "raycast_vertex_l1",
+        "raycast_normal_l1", "volume_columns_xy", "volume_tsdf", "volume_weight", "volume_rgb"))
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["pose_record"].shape == (5, 4, 4) and got["raycast_vertex_l0"].shape == (24, 3)
+    assert (got["raycast_normal_l1"] == -2.0).all() and got["raycast_vertex_l1"].shape == (6, 3)
+    assert got["volume_tsdf"].shape == (5, 16) and (got["volume_weight"][:, 3] == 103).all()
+    assert got["volume_rgb"].shape == (5, 48) and (got["volume_rgb"][0, :3] == (7, 8, 9)).all()
+    assert np.array_equal(got["volume_columns_xy"], np.load(tmp_path / "b" / "volume_columns_xy.npy"))
+
+
+def test_fit_dump_keeps_a_seeded_sample_within_the_limit():
+    import numpy as np
+    b = load_bench()
+    big = np.arange(600_000, dtype=np.float32).reshape(-1, 3)  # 2.4 MB
+    small = np.ones((4, 4), np.float32)
+    same = b.fit_dump({"big": big, "small": small}, limit=4 << 20)
+    assert same["big"] is big
+    cut = b.fit_dump({"big": big, "small": small}, limit=1 << 20)
+    assert sum(v.nbytes for v in cut.values()) <= 1 << 20 and cut["small"] is small
+    assert 0 < cut["big"].shape[0] < big.shape[0] and (np.diff(cut["big"][:, 0]) > 0).all()
+    again = b.fit_dump({"big": big, "small": small}, limit=1 << 20)
+    assert np.array_equal(cut["big"], again["big"])
+
+
 def test_imbalance():
     b = load_bench()
     assert b.imbalance([1.0, 1.0]) == 1.0

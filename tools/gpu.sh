@@ -51,7 +51,7 @@ for job in "$@"; do
     smoke)
       step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
     bench)
-      A=${val:---steps,20,--warmup,5}
+      A=--full,${val:---steps,20,--warmup,5}
       step bench 600 python3 bench.py $(args "$A") > gpurun_out/bench.json 2> gpurun_out/bench.err
       python3 -c "import json;d=json.loads(open('gpurun_out/bench.json').read().strip().splitlines()[-1]);print('bench',d['value'],d['ms_per_step'],d['timed_region_kernel_ms'])" ;;
     quick)

@@ -20,7 +20,7 @@ for v in "$@"; do
     i=$((i+1))
     echo "=== $v pass $i: $p"
     KFX_LIB_PATH=$L timeout -k 10 120 rocprofv3 --pmc $p --output-format csv -d "$ROOT/gpurun_out/pmcs/$v/p$i" -- \
-        python3 "$ROOT/bench.py" --steps 40 --warmup 100 --profile-frames 2 --cpu-frames 0 \
+        python3 "$ROOT/bench.py" --full --steps 40 --warmup 100 --profile-frames 2 --cpu-frames 0 \
         > "$ROOT/gpurun_out/pmcs/$v/p$i.log" 2>&1 || { echo "rc=$?"; tail -5 "$ROOT/gpurun_out/pmcs/$v/p$i.log"; exit 1; }
   done
 done

@@ -10,7 +10,7 @@ for v in "$@"; do
   [ "$v" = base ] && L="$ROOT/slam-kinectfusion_amd/lib/libkfx.so"
   KFX_LIB_PATH="$L" timeout -k 10 120 rocprofv3 --pmc $CTR --output-format csv \
       -d "$ROOT/gpurun_out/pmcv/$v" -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --profile-frames 2 --cpu-frames 0 --c1-frames 0 --c3-frames 0 --c5-frames 0 \
-      --host-frames 0 --extract 0 \
+      --host-frames 0 --extract 0 --full \
       > "$ROOT/gpurun_out/pmcv/$v.log" 2>&1 || { echo "rc=$?"; tail -5 "$ROOT/gpurun_out/pmcv/$v.log"; exit 1; }
 done
 for v in "$@"; do

@@ -9,7 +9,7 @@
 set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-ARGS="$*"   # the stats pass runs bench.py with these (default: its defaults)
+ARGS="--full $*"   # the stats pass runs bench.py with these (default: its defaults, side records included)
 # same frames and step counts as the stats pass; no side runs (the PMC record
 # averages every dispatch of a kernel, so only the main stream may launch it)
 PMC_ARGS="$ARGS --cpu-frames 0 --c1-frames 0 --c3-frames 0 --c5-frames 0 --host-frames 0"
