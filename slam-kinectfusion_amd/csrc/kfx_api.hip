@@ -87,6 +87,59 @@ constexpr int kInitialPoseCap = 1 << 16;
 // [7] / [8] a group combine's shared part (reductions, masks, resume) starts / ends
 constexpr int kStageEvents = 9;
 
+// How one frame's ICP / integrate / raycast are enqueued (frame_plan derives
+// it; enqueue_track, enqueue_map and record_icp_event follow it).
+struct FramePlan {
+  bool begin = false;           // frame_begin is folded into the ICP (overlapped frames: the preprocess ran on pstream)
+  unsigned sig = 0;             // the raycast stores this serial to start_sig as it starts (0: no signal)
+  bool order_in_stream = true;  // k_int_order follows the integrate on the frame stream
+                                // (false: the next overlapped frame launches it on pstream)
+  enum IcpEv { kNone, kAfterIcp, kAfterInt } icp_ev = kNone;  // where ev_icp is recorded
+  bool icp_ev_node = false;     // ... as an event-record node of the graph being captured
+};
+
+// What the last overlapped frame left for the next one (enqueue_frame_overlap
+// reads it at its start and rewrites it at its end; nothing else writes it).
+//
+// Overlapped frame k runs its preprocess on pstream into buffer set p = k & 1
+// and its ICP / integrate / raycast on the frame stream, which waits for
+// ev_prep (recorded on pstream behind the preprocess).  Frame k's pstream work
+// always starts behind ONE wait on frame k-1, the "start wait": for
+// start_sig >= sig when frame k-1's raycast signals its start (sig != 0), else
+// for ev_icp, which frame k-1 recorded behind its integrate.  Either way it
+// completes only after frame k-1's integrate has, and the frame stream is in
+// order, so after everything enqueued on the frame stream before that
+// integrate.  (DESIGN.md §13 has the measurements behind this schedule.)
+//
+//  - Buffer set p.  Its last user is frame k-2's ICP / integrate / raycast, on
+//    the frame stream before frame k-1's integrate: when `chained`, the start
+//    wait alone orders the preprocess after it, and no ev_free[p] record was
+//    or is made (each record between two frame kernels costs the frame stream
+//    2-5 us).  Otherwise the preprocess also waits for ev_free[p], which the
+//    last user of set p recorded at its end (free_rec[p]) or which is recorded
+//    now, at the frame stream's tail.
+//  - k_int_order (deep volumes: it rewrites the tile order the integrate reads)
+//    runs on pstream between the preprocess and the ev_prep record when
+//    order_pending.  The start wait orders it after frame k-1's integrate, the
+//    one that read the old order and left the intervals it sorts; ev_prep,
+//    which the frame stream waits for before frame k's ICP, orders it before
+//    the integrate that reads the new order.  Neither depends on ev_free: with
+//    the ev_free record elided the start wait is still enqueued, and it is
+//    that wait, not ev_free, that orders the cross-stream k_int_order.
+//  - `chained` holds only if the API call before this one (api_seq) enqueued
+//    frame k-1.  Any call in between (a single-stream frame into set 0, a
+//    stage hook, a group call) may have put work on the frame stream behind
+//    frame k-1's integrate that uses set p or runs an integrate, which the
+//    start wait does not cover: the chain is broken, and the ev_free[p] wait at
+//    the stream's tail orders the preprocess and k_int_order after that work.
+struct OverlapCarry {
+  bool chained = false;              // the frame provides the start wait (signal, or ev_icp behind its integrate) ...
+  unsigned long long api_seq = 0;    // ... and was enqueued by this API call
+  unsigned sig = 0;                  // the serial its raycast signals (0: it recorded ev_icp)
+  bool order_pending = false;        // its integrate left k_int_order to the next frame's pstream
+  bool free_rec[2]{};                // the last frame that used set p recorded ev_free[p]
+};
+
 struct kfx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -113,24 +166,15 @@ struct kfx_ctx {
   bool overlap = true;
   hipStream_t pstream = nullptr;
   hipEvent_t ev_prep = nullptr, ev_free[2]{};
-  // ev_free[p] elision (enqueue_frame_overlap): free_rec[p] = the last frame
-  // that used set p recorded ev_free[p]; ov_linked = the last API call into
-  // this context (api_seq, counted by check_ctx) enqueued an overlapped frame
-  // whose ev_icp record follows its integrate
-  bool free_rec[2]{};
-  bool ov_linked = false;
-  unsigned long long api_seq = 0, ov_api_seq = 0;
-  hipEvent_t ev_icp = nullptr;  // after the last overlapped frame's ICP, or its integrate (KFX_PREP_AFTER_INT): the next preprocess starts there
+  unsigned long long api_seq = 0;  // API calls into this context (counted by check_ctx)
+  hipEvent_t ev_icp = nullptr;  // after the last overlapped frame's integrate (a group member: its ICP): the next preprocess starts there
   hipEvent_t ev_group = nullptr;  // kfx_pipeline_group combine: fork (member 0) / join (the others)
-  // raycast start signal (KFX_PREP_SIG): fine-grained word the frame's raycast
-  // stores sig_serial to as it starts; the next preprocess waits for it with
+  // raycast start signal: fine-grained word an overlapped frame's raycast
+  // stores its serial to as it starts; the next preprocess waits for it with
   // hipStreamWaitValue32 on its own stream (null: unsupported, ev_icp instead)
   unsigned *start_sig = nullptr;
-  unsigned sig_serial = 0;
-  bool sig_prev = false;    // the last overlapped frame signalled sig_serial
-  bool ray_sig_on = false;  // enqueue_map: pass the signal to this raycast
-  bool ov_order = false, ov_order_prev = false;    // enqueue_map: the next preprocess stream launches k_int_order (KFX_ORDER_OFF_PATH)
-  unsigned frame_sig = 0;   // the serial the frame run_frame just enqueued signals (0: none)
+  unsigned sig_serial = 0;  // the last serial handed out (serials only grow: the word holds the latest one stored)
+  OverlapCarry ov;          // what the last overlapped frame left for the next one
   bool group_chain = false;     // kfx_pipeline_group member: record ev_icp after every ICP
   bool graphs_stale = false;    // a refused persistent ICP launch: captured graphs still hold it
 
@@ -168,7 +212,6 @@ struct kfx_ctx {
   // pyrDown/preprocess graph (pstream), [4i+2p+1] the ICP/integrate/raycast graph
   std::vector<hipGraphExec_t> ov_graph;
   bool ov_graph_full = false;  // also capture ICP/integrate/raycast (kfx_set_graph_mode 2)
-  bool cap_ext = false;        // capturing: the ev_icp record becomes an event-record node
   bool ov_main_refused = false;  // the main graph's capture failed (RCCL refused capture): eager
   hipError_t cap_err = hipSuccess;  // the last capture's HIP error (capture_graph)
   std::string graph_note;           // why the main graph was dropped (kfx_get_graph_note)
@@ -238,25 +281,6 @@ int dalloc(kfx_ctx *c, void **p, size_t bytes) {
   return KFX_OK;
 }
 
-#ifndef KFX_PREP_AFTER_ICP
-#define KFX_PREP_AFTER_ICP 1  // overlapped frames: next preprocess waits for this frame's ICP
-#endif
-#ifndef KFX_PREP_SIG
-#define KFX_PREP_SIG 1  // overlapped frames: the raycast's start signal replaces the ev_icp record
-#endif
-#ifndef KFX_ORDER_OFF_PATH
-#define KFX_ORDER_OFF_PATH 1  // overlapped frames: k_int_order on the preprocess stream, beside the raycast
-#endif
-#ifndef KFX_FREE_ELIDE
-#define KFX_FREE_ELIDE 1  // overlapped frames: no ev_free record when the next frame's ev_icp wait covers it
-#endif
-#ifndef KFX_PREP_AFTER_INT
-// ... for this frame's integrate instead: the preprocess then shares the GPU
-// with the raycast (memory-latency bound, 0.2-0.4 VALU issue) rather than the
-// issue-bound integrate; C2 integrate -12 us, raycast +8 us, frame -0.4 to
-// -1.4 % (7 alternating pairs)
-#define KFX_PREP_AFTER_INT 1
-#endif
 #ifndef KFX_COST_UPDATED
 #define KFX_COST_UPDATED 32  // slab balancing: weight of an updated voxel (64 = one visited slot; slice_cost)
 #endif
@@ -311,11 +335,11 @@ struct FrameInput {
   hipEvent_t done = nullptr;
 };
 
-// ev_icp behind the ICP just enqueued on s.  While a graph is being captured
-// (cap_ext) the record is added as an event-record node on the captured ICP,
-// so every replay records the event for the next frame's preprocess.
-int record_icp_event(kfx_ctx *c, hipStream_t s) {
-  if (!c->cap_ext) {
+// ev_icp behind the work just enqueued on s.  While a graph is being captured
+// (as_node) the record is added as an event-record node behind the captured
+// kernels, so every replay records the event for the next frame's preprocess.
+int record_icp_event(kfx_ctx *c, hipStream_t s, bool as_node) {
+  if (!as_node) {
     HIPCHK(hipEventRecord(c->ev_icp, s));
     return KFX_OK;
   }
@@ -338,24 +362,62 @@ int record_icp_event(kfx_ctx *c, hipStream_t s) {
 // [4] after raycast (+ slab combine); [0..1] are absent for overlapped frames.
 // Slab contexts stop after their local raycast (enqueue_local) and then
 // combine the slabs' raycast results (enqueue_combine).
-void enqueue_pre(kfx_ctx *c, FrameInput in, hipEvent_t *ev);
+void enqueue_pre(kfx_ctx *c, FrameInput in, hipStream_t s, DevState *st, hipEvent_t *ev = nullptr);
 void enqueue_local(kfx_ctx *c, FrameInput in, hipEvent_t *ev);
-int enqueue_track(kfx_ctx *c, FrameInput in, hipEvent_t *ev, bool begin);
+int enqueue_track(kfx_ctx *c, FrameInput in, hipEvent_t *ev, const FramePlan &plan);
 int enqueue_combine(kfx_ctx *c);
 void enqueue_slab_resume(kfx_ctx *c, hipStream_t s);
 
-int enqueue_frame(kfx_ctx *c, FrameInput in, hipEvent_t *ev) {
-  enqueue_pre(c, in, ev);
-  int r = enqueue_track(c, in, ev, false);
-  if (ev) (void)hipEventRecord(ev[5], c->stream);
+// The three ways a frame's ICP / integrate / raycast are enqueued, and the one
+// place that decides what each does about the cross-frame hand-offs.
+enum class FrameKind {
+  kSingleStream,  // preprocess and the rest on the frame stream (kfx_pipeline, group members, stage hooks)
+  kOverlapEager,  // overlapped frame, launched eagerly on the frame stream
+  kOverlapGraph,  // overlapped frame whose main part is a graph (being captured, or replayed: graph mode 2)
+};
+FramePlan frame_plan(const kfx_ctx *c, FrameKind kind) {
+  FramePlan f;
+  if (kind != FrameKind::kSingleStream) f.begin = true;
+  if (c->group_chain) {  // the next same-device member's ICP starts behind this one
+    f.icp_ev = FramePlan::kAfterIcp;
+  } else if (kind == FrameKind::kOverlapGraph) {
+    // a graph's launch arguments are fixed (no serial), and it holds its own
+    // k_int_order launch: the next preprocess starts behind its ev_icp node
+    f.icp_ev = FramePlan::kAfterInt;
+    f.icp_ev_node = true;
+  } else if (kind == FrameKind::kOverlapEager) {
+    // The next preprocess starts behind this frame's integrate: it then shares
+    // the GPU with the raycast (memory-latency bound, 0.2-0.4 VALU issue)
+    // rather than the latency-bound persistent ICP or the issue-bound
+    // integrate (C2 frame -0.4 to -1.4 %).  The raycast's start
+    // signal says so without an event record on the frame stream; without the
+    // signal (start_sig null) ev_icp is recorded behind the integrate.
+    // k_int_order runs on the next frame's pstream, beside the raycast.
+    f.order_in_stream = false;
+    if (c->start_sig) f.sig = c->sig_serial + 1;
+    else f.icp_ev = FramePlan::kAfterInt;
+  }
+  return f;
+}
+
+// The stage events behind a frame's local raycast and its slab combine;
+// end: also record ev[4] behind a single volume's frame (profiled frames end there)
+int enqueue_frame_tail(kfx_ctx *c, hipEvent_t *ev, int r, bool end) {
+  if (ev) HIPCHK(hipEventRecord(ev[5], c->stream));
   if (ev && c->slab) {  // (a single volume's sample ends at [5]: no combine to time)
-    (void)hipEventRecord(ev[6], c->stream);
-    (void)hipEventRecord(ev[7], c->stream);  // (no shared part: [7] = [8])
-    (void)hipEventRecord(ev[8], c->stream);
+    HIPCHK(hipEventRecord(ev[6], c->stream));
+    HIPCHK(hipEventRecord(ev[7], c->stream));  // (no shared part: [7] = [8])
+    HIPCHK(hipEventRecord(ev[8], c->stream));
   }
   if (!r && c->slab) r = enqueue_combine(c);
-  if (ev) (void)hipEventRecord(ev[4], c->stream);  // (the profiled frames' end)
+  if (ev && (end || c->slab)) HIPCHK(hipEventRecord(ev[4], c->stream));
   return r;
+}
+
+int enqueue_frame(kfx_ctx *c, FrameInput in, hipEvent_t *ev) {
+  enqueue_pre(c, in, c->stream, c->st, ev);
+  const int r = enqueue_track(c, in, ev, frame_plan(c, FrameKind::kSingleStream));
+  return enqueue_frame_tail(c, ev, r, true);
 }
 
 #define NCCLCHK(expr)                                                                      \
@@ -390,20 +452,21 @@ int enqueue_combine(kfx_ctx *c) {
   return KFX_OK;
 }
 
-// imageProcess (kinectfusion.cpp:48-76) into the current set
-void enqueue_pre(kfx_ctx *c, FrameInput in, hipEvent_t *ev) {
-  hipStream_t s = c->stream;
+// imageProcess (kinectfusion.cpp:48-76) into the current set, on stream s;
+// st: the frame state frame_begin resets (null for an overlapped frame's
+// preprocess on pstream: its ICP folds frame_begin in)
+void enqueue_pre(kfx_ctx *c, FrameInput in, hipStream_t s, DevState *st, hipEvent_t *ev) {
   if (ev) (void)hipEventRecord(ev[0], s);
   const float *raw[kMaxLevels];
   for (int l = 0; l < kMaxLevels; ++l) raw[l] = c->raw[l];
   raw[0] = in.d32;
   if (c->L > 1) {
-    launch_pyr_down(s, in.d32, in.d16, c->g[0].w, c->g[0].h, c->raw[1], c->st, c->dl0);
+    launch_pyr_down(s, in.d32, in.d16, c->g[0].w, c->g[0].h, c->raw[1], st, c->dl0);
     for (int l = 2; l < c->L; ++l)
       launch_pyr_down(s, c->raw[l - 1], nullptr, c->g[l - 1].w, c->g[l - 1].h, c->raw[l], nullptr,
                       nullptr);
   } else {
-    launch_frame_begin(s, c->st, c->dl0, c->g[0]);
+    launch_frame_begin(s, st, c->dl0, c->g[0]);
   }
   launch_preprocess_maps(s, c->L, raw, in.d16, c->g, c->cur, c->p.bfilter_kernel_size,
                          c->p.bfilter_color_sigma, c->p.bfilter_spatial_sigma, c->p.dfilter_dist,
@@ -412,8 +475,8 @@ void enqueue_pre(kfx_ctx *c, FrameInput in, hipEvent_t *ev) {
 }
 
 void enqueue_local(kfx_ctx *c, FrameInput in, hipEvent_t *ev) {
-  enqueue_pre(c, in, ev);
-  (void)enqueue_track(c, in, ev, false);
+  enqueue_pre(c, in, c->stream, c->st, ev);
+  (void)enqueue_track(c, in, ev, frame_plan(c, FrameKind::kSingleStream));
 }
 
 // Sharded ICP (kfx_set_icp_allreduce): this rank's band of
@@ -458,18 +521,18 @@ void enqueue_slab_resume(kfx_ctx *c, hipStream_t s) {
 }
 
 // integrate + raycast of the frame whose maps are in the current set
-int enqueue_map(kfx_ctx *c, FrameInput in, hipEvent_t *ev, bool rec_int = false) {
+int enqueue_map(kfx_ctx *c, FrameInput in, hipEvent_t *ev, const FramePlan &plan) {
   hipStream_t s = c->stream;
   launch_integrate(s, c->vol, c->g[0], c->dl0, c->cur.d[0], c->inv_lambda, in.bgr, c->st, c->pose_log,
-                   to_dev(c->p.volu_pose), nullptr, nullptr, !c->ov_order);
+                   to_dev(c->p.volu_pose), nullptr, nullptr, plan.order_in_stream);
   if (ev) (void)hipEventRecord(ev[3], s);
-  if (rec_int) {
-    const int r = record_icp_event(c, s);
+  if (plan.icp_ev == FramePlan::kAfterInt) {
+    const int r = record_icp_event(c, s, plan.icp_ev_node);
     if (r) return r;
   }
   launch_raycast(s, c->vol, c->L, c->g, c->cur, c->prev, c->st, c->pose_log,
                  to_dev(c->p.volu_pose), nullptr, c->slab ? c->key_local : nullptr, nullptr, slab_pass1(c),
-                 c->ray_sig_on ? c->start_sig : nullptr, c->sig_serial);
+                 plan.sig ? c->start_sig : nullptr, plan.sig);
   return KFX_OK;
 }
 
@@ -485,10 +548,10 @@ bool try_icp_persistent(kfx_ctx *c, hipStream_t s, int begin) {
   return false;
 }
 
-// ICP, integrate and raycast of the frame whose maps are in the current set;
-// begin: the frame's frame_begin has not run yet (overlapped frames)
-int enqueue_track(kfx_ctx *c, FrameInput in, hipEvent_t *ev, bool begin) {
+// ICP, integrate and raycast of the frame whose maps are in the current set
+int enqueue_track(kfx_ctx *c, FrameInput in, hipEvent_t *ev, const FramePlan &plan) {
   hipStream_t s = c->stream;
+  const bool begin = plan.begin;  // the frame's frame_begin has not run yet
   // ICPRegistration::rigidTransform (icp_registration.cpp:16-46)
   int r = KFX_OK;
   if (c->icp_sharded && c->comm) {
@@ -503,12 +566,11 @@ int enqueue_track(kfx_ctx *c, FrameInput in, hipEvent_t *ev, bool begin) {
     }
   }
   if (ev) (void)hipEventRecord(ev[2], s);
-  // overlapped frames: the next preprocess waits here; a group: the next
-  // member's ICP on this device waits here
-  // (with the raycast start signal the next preprocess waits for that instead)
-  const bool after_int = KFX_PREP_AFTER_INT && begin && !c->group_chain && !c->ray_sig_on;
-  if ((begin || c->group_chain) && !after_int && !c->ray_sig_on && !r && (r = record_icp_event(c, s))) return r;
-  const int rm = enqueue_map(c, in, ev, after_int && !r);
+  // a group: the next member's ICP on this device waits here
+  if (plan.icp_ev == FramePlan::kAfterIcp && !r && (r = record_icp_event(c, s, plan.icp_ev_node))) return r;
+  FramePlan map = plan;
+  if (r) map.icp_ev = FramePlan::kNone;  // (a failed sharded ICP: no hand-off)
+  const int rm = enqueue_map(c, in, ev, map);
   return r ? r : rm;
 }
 
@@ -519,121 +581,70 @@ int enqueue_track(kfx_ctx *c, FrameInput in, hipEvent_t *ev, bool begin) {
 // cross-stream dependencies: ~9 us/frame for the wait on ev_prep, while
 // dropping the ev_free ordering (unsafe) is slower, as preprocess then
 // competes with integrate/raycast.
-// pyrDown + preprocess of an overlapped frame into the current set, on pstream.
-void enqueue_prep_overlap(kfx_ctx *c, FrameInput in) {
-  hipStream_t b = c->pstream;
-  const float *raw[kMaxLevels];
-  for (int l = 0; l < kMaxLevels; ++l) raw[l] = c->raw[l];
-  raw[0] = in.d32;
-  if (c->L > 1) {
-    launch_pyr_down(b, in.d32, in.d16, c->g[0].w, c->g[0].h, c->raw[1], nullptr, c->dl0);
-    for (int l = 2; l < c->L; ++l)
-      launch_pyr_down(b, c->raw[l - 1], nullptr, c->g[l - 1].w, c->g[l - 1].h, c->raw[l], nullptr,
-                      nullptr);
-  } else {
-    launch_frame_begin(b, nullptr, c->dl0, c->g[0]);
-  }
-  launch_preprocess_maps(b, c->L, raw, in.d16, c->g, c->cur, c->p.bfilter_kernel_size,
-                         c->p.bfilter_color_sigma, c->p.bfilter_spatial_sigma, c->p.dfilter_dist,
-                         c->inv_lambda, c->dl0);
-}
 
 // ICP (frame_begin folded in) + integrate + raycast (+ slab combine) of an
 // overlapped frame, on the frame stream.
-int enqueue_main_overlap(kfx_ctx *c, FrameInput in, hipEvent_t *ev) {
+int enqueue_main_overlap(kfx_ctx *c, FrameInput in, hipEvent_t *ev, const FramePlan &plan) {
   if (ev) HIPCHK(hipEventRecord(ev[1], c->stream));
-  int r = enqueue_track(c, in, ev, true);
-  if (ev) HIPCHK(hipEventRecord(ev[5], c->stream));
-  if (ev && c->slab) {  // (a single volume's sample ends at [5])
-    HIPCHK(hipEventRecord(ev[6], c->stream));
-    HIPCHK(hipEventRecord(ev[7], c->stream));
-    HIPCHK(hipEventRecord(ev[8], c->stream));
-  }
-  if (!r && c->slab) r = enqueue_combine(c);
-  if (ev && c->slab) HIPCHK(hipEventRecord(ev[4], c->stream));
-  return r;
+  const int r = enqueue_track(c, in, ev, plan);
+  return enqueue_frame_tail(c, ev, r, false);
 }
 
 // gx (optional): this frame's two captured graphs for the set it uses
 // (ensure_ov_graphs), replayed in place of the eager launches; the cross-frame
 // and cross-stream event waits stay around them.
+// The waits and hand-offs are those of OverlapCarry's invariants.
 int enqueue_frame_overlap(kfx_ctx *c, FrameInput in, hipEvent_t *ev, hipGraphExec_t *gx) {
   const int p = c->par ^ 1;
   set_par(c, p);
   hipStream_t b = c->pstream;
-  // Set p was last used by the frame before last.  When the previous API call
-  // enqueued the previous overlapped frame and that frame records ev_icp after
-  // its integrate, the ev_icp wait below already orders this preprocess after
-  // that frame's integrate, and so (one in-order stream) after everything
-  // enqueued on the frame stream before it — the frame before last included:
-  // no ev_free record is needed (each record between two frame kernels costs
-  // the frame stream 2-5 us).  Otherwise wait for ev_free[p],
-  // recorded now at the frame stream's tail if its last user did not record it.
-  const bool linked = KFX_FREE_ELIDE && KFX_PREP_AFTER_ICP && c->ov_linked && c->api_seq == c->ov_api_seq + 1;
-  if (!linked) {
-    if (!c->free_rec[p]) HIPCHK(hipEventRecord(c->ev_free[p], c->stream));
+  OverlapCarry &ov = c->ov;
+  // set p is free: by the start wait below when the previous API call chained
+  // the previous frame, else by ev_free[p]
+  const bool chained = ov.chained && c->api_seq == ov.api_seq + 1;
+  if (!chained) {
+    if (!ov.free_rec[p]) HIPCHK(hipEventRecord(c->ev_free[p], c->stream));
     HIPCHK(hipStreamWaitEvent(b, c->ev_free[p], 0));  // the frame before last is done with set p
   }
-  c->ov_linked = false;
-  c->free_rec[p] = false;
+  ov.chained = false;
+  ov.free_rec[p] = false;
   if (in.ready) HIPCHK(hipStreamWaitEvent(b, in.ready, 0));  // host input uploaded
-#if KFX_PREP_AFTER_ICP
-  // start behind the previous frame's ICP (KFX_PREP_AFTER_INT: its integrate;
-  // ev_icp is recorded there; KFX_PREP_SIG: as its raycast starts, which
-  // stores the frame's serial): the latency-bound persistent ICP then runs
-  // alone and the preprocess shares the GPU with the raycast
-  if (c->sig_prev)
-    HIPCHK(hipStreamWaitValue32(b, c->start_sig, c->sig_serial, hipStreamWaitValueGte, 0xffffffffu));
+  // the start wait: behind the previous frame's integrate
+  if (ov.sig)
+    HIPCHK(hipStreamWaitValue32(b, c->start_sig, ov.sig, hipStreamWaitValueGte, 0xffffffffu));
   else
     HIPCHK(hipStreamWaitEvent(b, c->ev_icp, 0));
-#endif
   if (gx) HIPCHK(hipGraphLaunch(gx[0], b));
-  else enqueue_prep_overlap(c, in);
-  // the dispatch order of this frame's integrate from the previous frame's
-  // intervals, off the frame stream: the wait above (its raycast has started,
-  // or ev_icp behind its integrate) orders it after the integrate that read
-  // the old order, and ev_prep before this frame's integrate
-  if (c->ov_order_prev) launch_int_order(b, c->vol);
+  else enqueue_pre(c, in, b, nullptr);
+  if (ov.order_pending) launch_int_order(b, c->vol);
   HIPCHK(hipEventRecord(c->ev_prep, b));
   HIPCHK(hipStreamWaitEvent(c->stream, c->ev_prep, 0));
+  const bool graph = gx && gx[1];
+  FramePlan plan = frame_plan(c, graph ? FrameKind::kOverlapGraph : FrameKind::kOverlapEager);
+  ov.sig = 0u;
+  if (plan.sig > 0x7fffffffu) {  // wrap: restart the serials from a drained context
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(b));
+    if (c->cstream) HIPCHK(hipStreamSynchronize(c->cstream));
+    HIPCHK(hipMemset(c->start_sig, 0, 64));
+    for (unsigned &v : c->ring_sig) v = 0u;  // (their frames are complete)
+    plan.sig = 1u;
+  }
+  if (plan.sig) c->sig_serial = plan.sig;
   int r = KFX_OK;
-  // this frame's raycast signals its start (not inside a captured main graph,
-  // whose launch arguments are fixed: it records ev_icp)
-  const bool use_sig = KFX_PREP_SIG && KFX_PREP_AFTER_ICP && KFX_PREP_AFTER_INT && c->start_sig && !c->group_chain &&
-                       !(gx && gx[1]);
-  c->sig_prev = false;
-  if (use_sig) {
-    if (c->sig_serial >= 0x7fffffffu) {  // wrap: restart the serials from a drained context
-      HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(hipStreamSynchronize(b));
-      if (c->cstream) HIPCHK(hipStreamSynchronize(c->cstream));
-      HIPCHK(hipMemset(c->start_sig, 0, 64));
-      c->sig_serial = 0;
-      for (unsigned &v : c->ring_sig) v = 0u;  // (their frames are complete)
-    }
-    c->sig_serial += 1;
-    c->ray_sig_on = true;
-  }
-  // (not for a captured main graph: it holds its own k_int_order launch)
-  c->ov_order = KFX_ORDER_OFF_PATH && KFX_PREP_AFTER_ICP && KFX_PREP_AFTER_INT && !c->group_chain && !(gx && gx[1]);
-  if (gx && gx[1]) HIPCHK(hipGraphLaunch(gx[1], c->stream));
-  else r = enqueue_main_overlap(c, in, ev);
-  c->ray_sig_on = false;
-  c->ov_order_prev = c->ov_order && !r;
-  c->ov_order = false;
-  c->sig_prev = use_sig && !r;
-  c->frame_sig = c->sig_prev ? c->sig_serial : 0u;
-  // the next overlapped frame may rely on this frame's ev_icp (recorded after
-  // its integrate: enqueue_track) instead of ev_free[p]
-  const bool link = KFX_FREE_ELIDE && KFX_PREP_AFTER_ICP && KFX_PREP_AFTER_INT && !c->group_chain && !r;
-  if (!link) {
+  if (graph) HIPCHK(hipGraphLaunch(gx[1], c->stream));
+  else r = enqueue_main_overlap(c, in, ev, plan);
+  ov.sig = r ? 0u : plan.sig;
+  ov.order_pending = !plan.order_in_stream && !r;
+  // the frame provides the next one's start wait; else it records ev_free[p]
+  ov.chained = (plan.sig || plan.icp_ev == FramePlan::kAfterInt) && !r;
+  ov.api_seq = c->api_seq;
+  if (!ov.chained) {
     HIPCHK(hipEventRecord(c->ev_free[p], c->stream));
-    c->free_rec[p] = true;
+    ov.free_rec[p] = true;
   }
-  c->ov_linked = link;
-  c->ov_api_seq = c->api_seq;
   // (a signalling frame's input slot is released by its raycast start signal)
-  if (in.done && !c->frame_sig) HIPCHK(hipEventRecord(in.done, c->stream));
+  if (in.done && !ov.sig) HIPCHK(hipEventRecord(in.done, c->stream));
   return r;
 }
 
@@ -681,11 +692,10 @@ int ensure_ov_graphs(kfx_ctx *c, FrameInput in, hipGraphExec_t *gx, int p) {
   const int keep = c->par;
   set_par(c, p);
   int r = gx[0] ? KFX_OK
-                : capture_graph(c, c->pstream, [&] { enqueue_prep_overlap(c, in); return KFX_OK; }, &gx[0]);
+                : capture_graph(c, c->pstream, [&] { enqueue_pre(c, in, c->pstream, nullptr); return KFX_OK; }, &gx[0]);
   if (!r && !gx[1] && main) {
-    c->cap_ext = true;
-    r = capture_graph(c, c->stream, [&] { return enqueue_main_overlap(c, in, nullptr); }, &gx[1]);
-    c->cap_ext = false;
+    const FramePlan plan = frame_plan(c, FrameKind::kOverlapGraph);
+    r = capture_graph(c, c->stream, [&] { return enqueue_main_overlap(c, in, nullptr, plan); }, &gx[1]);
     // only a collective that refused capture (an RCCL error inside the
     // capture, or a capture the runtime reports unsupported / invalidated)
     // drops the main graph for good; every other failure is returned
@@ -777,8 +787,10 @@ hipEvent_t *timing_sample(kfx_ctx *c) {
 // overlap: the input stays valid until the frame completes (staged frames)
 // ovg: the input's four overlapped-frame graphs (ensure_ov_graphs, two per
 // buffer set), or null for eager overlapped launches
+// sig (optional): receives the serial the frame's raycast signals as it starts
+// (0: none; the frame then records in.done)
 int run_frame(kfx_ctx *c, FrameInput in, hipGraphExec_t *graph, bool overlap = false,
-              hipGraphExec_t *ovg = nullptr) {
+              hipGraphExec_t *ovg = nullptr, unsigned *sig = nullptr) {
   int r = ensure_pose_capacity(c, 1);
   if (r) return r;
   if (c->graphs_stale) {  // captured with the persistent ICP launch the runtime refused
@@ -788,7 +800,7 @@ int run_frame(kfx_ctx *c, FrameInput in, hipGraphExec_t *graph, bool overlap = f
     c->graphs_stale = false;
   }
   c->last_bgr = in.bgr;
-  c->frame_sig = 0u;
+  if (sig) *sig = 0u;
   hipEvent_t *tev = timing_sample(c);  // this frame's timing sample, if sampled
   if (overlap && c->overlap && !c->profiling) {
     hipGraphExec_t *gx = nullptr;
@@ -797,6 +809,7 @@ int run_frame(kfx_ctx *c, FrameInput in, hipGraphExec_t *graph, bool overlap = f
       if ((r = ensure_ov_graphs(c, in, gx, c->par ^ 1))) return r;
     }
     if ((r = enqueue_frame_overlap(c, in, tev, gx))) return r;
+    if (sig) *sig = c->ov.sig;
     HIPCHK(hipGetLastError());
     c->pending += 1;
     return KFX_OK;
@@ -1171,7 +1184,7 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
     HIPCHK(hipMemcpy(c->vol.iperm, iota.data(), items * 4, hipMemcpyHostToDevice));
   }
   {
-    // the raycast start signal (KFX_PREP_SIG) needs hipStreamWaitValue32; it
+    // the raycast start signal needs hipStreamWaitValue32; it
     // is off under rocprofv3 counter collection (ROCPROF_COUNTER_COLLECTION),
     // whose per-dispatch serialisation hung on the waiting preprocess queue,
     // and with KFX_STREAM_SIGNAL=0 (events instead; results identical)
@@ -1377,8 +1390,9 @@ static int pipeline_async(kfx_ctx *c, const uint8_t *bgr, const void *depth, boo
   in.ready = c->ring_h2d[k];
   in.done = c->ring_done[k];
   c->ring_sig[k] = 0u;
-  r = run_frame(c, in, nullptr, true, c->ring_graph[k][u16 ? 1 : 0]);
-  if (!r) c->ring_sig[k] = c->frame_sig;
+  unsigned sig = 0u;
+  r = run_frame(c, in, nullptr, true, c->ring_graph[k][u16 ? 1 : 0], &sig);
+  if (!r) c->ring_sig[k] = sig;
   return r;
 }
 
@@ -2539,7 +2553,7 @@ static int slice_work_parts(kfx_ctx *c, const uint8_t *bgr, const float *depth_m
   const size_t np = (size_t)c->intr.width * c->intr.height;
   HIPCHK(hipMemcpyAsync(c->raw[0], depth_mm, np * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->bgr, bgr, np * 3, hipMemcpyHostToDevice, c->stream));
-  enqueue_pre(c, {c->raw[0], nullptr, c->bgr}, nullptr);  // the frame's {depth, 1/lambda} table and max depth
+  enqueue_pre(c, {c->raw[0], nullptr, c->bgr}, c->stream, c->st);  // the frame's {depth, 1/lambda} table and max depth
   const int Z = c->vol.Z;
   const size_t n = 2 * (size_t)Z + 1;
   unsigned long long *hist = nullptr;
@@ -2668,7 +2682,7 @@ int kfx_pipeline_group(kfx_ctx **cs, int n, const uint8_t *bgr, const float *dep
     HIPCHK(hipMemcpyAsync(c->bgr, bgr, np * 3, hipMemcpyHostToDevice, c->stream));
     c->last_bgr = c->bgr;
     if (sharded) {
-      enqueue_pre(c, {c->raw[0], nullptr, c->bgr}, nullptr);
+      enqueue_pre(c, {c->raw[0], nullptr, c->bgr}, c->stream, c->st);
     } else {
       // Two persistent ICP grids spinning on one device at once can each hold
       // CUs the other's grid barrier waits for (the watchdog then fires): a
@@ -2709,7 +2723,7 @@ int kfx_pipeline_group(kfx_ctx **cs, int n, const uint8_t *bgr, const float *dep
     for (int k = 0; k < n; ++k) {
       kfx_ctx *c = cs[k];
       if ((r = check_ctx(c))) return r;
-      enqueue_map(c, {c->raw[0], nullptr, c->bgr}, nullptr);
+      enqueue_map(c, {c->raw[0], nullptr, c->bgr}, nullptr, frame_plan(c, FrameKind::kSingleStream));
       HIPCHK(hipGetLastError());
     }
   }

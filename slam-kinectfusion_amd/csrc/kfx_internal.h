@@ -58,13 +58,10 @@ struct LevelGeom {
 
 #ifndef KFX_ICP_SHARDS
 // ICP: partial-sum rows (atomic spread vs rows every solver reads).  With the
-// flat arrival counter 4 measured best (C2 ICP -3 us vs 8); with the per-XCD
-// arrival counters (KFX_ICP_HIER) 8: tools/icp_barrier_bench.hip, 300 blocks
-// 4.35 us per hand-off at 4 shards, 3.33 at 8, 3.19 at 16
+// per-residue arrival counters (IcpSync::sub, top) 8 measured best:
+// tools/icp_barrier_bench.hip, 300 blocks 4.35 us per hand-off at 4 shards,
+// 3.33 at 8, 3.19 at 16 (a flat arrival counter preferred 4: DESIGN.md §13)
 #define KFX_ICP_SHARDS 8
-#endif
-#ifndef KFX_ICP_HIER
-#define KFX_ICP_HIER 1  // ICP arrival: per-residue (b % 8, one XCD each) counters, then a top counter of 8
 #endif
 constexpr int kIcpShards = KFX_ICP_SHARDS;
 constexpr int kIcpMaxSlots = 64;  // ICP iterations per frame in the persistent kernel
@@ -90,12 +87,12 @@ constexpr int kIcpStrideMax = 16;
 // Device workspace of the persistent ICP kernel; zero between launches
 // (the kernel's last block restores that).
 struct IcpSync {
-  unsigned arrive, pad0[31];   // arrivals, all iterations (own 128-B line)
+  unsigned rsv, pad0[31];      // reserved line (the layout is fixed: fields are addressed by offset); cleared with the counters
   unsigned exit, pad1[31];
   struct {
     unsigned v, pad[31];
-  } sub[8];                    // KFX_ICP_HIER: arrivals of the blocks b % 8 == r, all iterations
-  unsigned top, pad2[31];      // KFX_ICP_HIER: residues complete, all iterations
+  } sub[8];                    // arrivals of the blocks b % 8 == r (one XCD each), all iterations (own 128-B lines)
+  unsigned top, pad2[31];      // residues complete, all iterations: the last of 8 releases
   struct {
     unsigned v, pad[31];
   } release[8];                // iterations released so far; 8 copies polled by block % 8

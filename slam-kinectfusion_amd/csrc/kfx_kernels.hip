@@ -27,13 +27,11 @@
 #ifndef KFX_RAY_KR
 #define KFX_RAY_KR 14  // raycast: samples per batch (loads in flight per lane)
 #endif
-#ifndef KFX_RAY_HINT
-// raycast: waves whose tile was slow in the last frame (frames are temporally
-// coherent) take a higher issue priority (s_setprio) while all waves compete
-#define KFX_RAY_HINT 1
-#endif
 #ifndef KFX_RAY_HINT_T0
-#define KFX_RAY_HINT_T0 70  // priority thresholds, 1024-cycle units of last frame's wave duration
+// raycast: waves whose tile was slow in the last frame (frames are temporally
+// coherent) take a higher issue priority (s_setprio) while all waves compete;
+// the priority thresholds, in 1024-cycle units of last frame's wave duration
+#define KFX_RAY_HINT_T0 70
 #endif
 #ifndef KFX_INT_OCC
 #define KFX_INT_OCC 8  // integrate: waves per SIMD the register budget is sized for
@@ -166,39 +164,14 @@ __device__ __forceinline__ float div_rn(float x, float d, float y) {
   return fmaf(r, y, q0);
 }
 
-// The same sequences on two independent operands (v_pk_mul/v_pk_fma_f32: the
-// per-element IEEE operations of the scalar forms, two per instruction).
+// Two FP32 values in a register pair (the raycast's position / ray-length steps).
 typedef float pf2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ pf2 pfma(pf2 a, pf2 b, pf2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ pf2 rcp_rn2(pf2 d) {
-  const pf2 r = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-  return pfma(pfma(-d, r, pf2{1.f, 1.f}), r, r);
-}
-__device__ __forceinline__ pf2 div_rn2(pf2 x, pf2 d, pf2 y) {
-  const pf2 q0 = x * y;
-  return pfma(pfma(-q0, d, x), y, q0);
-}
-__device__ __forceinline__ pf2 sqrt_rn2(pf2 x) {
-  const pf2 y = {__builtin_amdgcn_rsqf(x.x), __builtin_amdgcn_rsqf(x.y)};
-  const pf2 s0 = x * y;
-  return pfma(pfma(-s0, s0, x), pf2{0.5f, 0.5f} * y, s0);
-}
 
-// Integrate's voxel pairs (ipf2): packed FP32 (KFX_INT_PK 1: v_pk_* ops,
-// each 4 cycles per wave on gfx950, tools/valu_calib.hip) or two scalar
-// operations per pair (0: 2 cycles each, no register moves to pair operands).
-#ifndef KFX_INT_LDALL
-#define KFX_INT_LDALL 1  // integrate: pin the batch's tsdf / weight loads before the update branches (C2 -1.5 us)
-#endif
-#ifndef KFX_INT_BSKIP
-#define KFX_INT_BSKIP 0  // integrate: skip a batch's loads and update when no voxel of the wave passes
-#endif
-#ifndef KFX_INT_PK
-#define KFX_INT_PK 0  // scalar pairs: C2 integrate 0.190 -> 0.178 ms with -fno-slp-vectorize
-#endif
-#if KFX_INT_PK
-typedef pf2 ipf2;
-#else
+// Integrate's voxel pairs (ipf2): the div_rn / rcp_rn / sqrt_rn sequences on
+// two independent operands, as two scalar operations per pair (2 cycles each per
+// wave on gfx950, no register moves to pair operands; C2 integrate 0.190 ->
+// 0.178 ms against packed v_pk_* FP32, 4 cycles each, tools/valu_calib.hip;
+// with -fno-slp-vectorize).
 struct ipf2 {
   float x, y;
   __device__ __forceinline__ float operator[](int k) const { return k ? y : x; }
@@ -221,7 +194,6 @@ __device__ __forceinline__ ipf2 sqrt_rn2(ipf2 x) {
   const ipf2 s0 = x * y;
   return pfma(pfma(-s0, s0, x), ipf2{0.5f, 0.5f} * y, s0);
 }
-#endif
 
 // Pixel coordinate rn((a / d) * f + c) as a float, with a / d from one
 // reciprocal y = RN(1/d) shared by both image axes: div_rn(a, d, y) is the
@@ -590,24 +562,12 @@ __global__ __launch_bounds__(256) void k_preprocess_maps(BilatArgs a) {
 // exact int64 fixed point (D; order-independent, so any reduction tree gives
 // the oracle's sums).  Each lane takes kIcpPix pixels whose loads are issued
 // together; the block reduces through LDS and writes one 27-word partial.
-#ifndef KFX_ICP_XCD
-#define KFX_ICP_XCD 1  // ICP: XCD-banded pixel rows per block
-#endif
 #ifndef KFX_ICP_PIX
 #define KFX_ICP_PIX 4
 #endif
 constexpr int kIcpPix = KFX_ICP_PIX;
-#ifndef KFX_EXTRACT_SKIP
-#define KFX_EXTRACT_SKIP 1  // point / mesh extraction: waves of clear bricks read nothing
-#endif
 #ifndef KFX_XSWEEP_WAVES
 #define KFX_XSWEEP_WAVES 65536  // extraction: units per wave grow (up to 64) while this many waves remain
-#endif
-#ifndef KFX_RAY_SLAB_SKIP
-#define KFX_RAY_SLAB_SKIP 1  // slab raycast: rays jump over the samples before the stored slices
-#endif
-#ifndef KFX_RAY_N32
-#define KFX_RAY_N32 1  // raycast normals: 32-bit tile-column offsets + buffer loads (kIdx32 volumes)
 #endif
 #ifndef KFX_ICP_PPLCAP
 #define KFX_ICP_PPLCAP 256  // ICP plan: a level takes the fewest pixels per lane that keep it within this many blocks
@@ -918,8 +878,7 @@ __global__ __launch_bounds__(kIcpThreads, KFX_ICP_MINB) void k_icp_track(IcpPlan
   __shared__ int sfail, sstall;
   int fail = 0;
   const bool withhold = blockIdx.x == 0 && st->debug_stall;  // test hook: never arrive at slot 0
-  unsigned target = 0;  // (flat arrival counter: KFX_ICP_HIER 0)
-  unsigned tsub = 0, ttop = 0;  // KFX_ICP_HIER: this block's residue's and the top counter's targets
+  unsigned tsub = 0, ttop = 0;  // arrival targets: this block's residue counter's and the top counter's
   int slot = 0;
   for (int l = pl.levels - 1; l >= 0 && !fail; --l) {
     const LevelGeom g = pl.g[l];
@@ -937,7 +896,7 @@ __global__ __launch_bounds__(kIcpThreads, KFX_ICP_MINB) void k_icp_track(IcpPlan
     // lane, held in registers like a group
     int lppl = pl.ppl[l];
     if (mine && !stride) {
-      const int r = KFX_ICP_XCD ? xcd_remap(blockIdx.x, pl.groups[l]) : (int)blockIdx.x;
+      const int r = xcd_remap(blockIdx.x, pl.groups[l]);  // XCD-banded pixel rows per block
       if (pl.span[l] > 0) {
         const int b0 = r * pl.span[l], b1 = min(pl.npix[l], b0 + pl.span[l]);
         lppl = min(kIcpPix, (b1 - b0 + kIcpThreads - 1) / kIcpThreads);
@@ -948,9 +907,7 @@ __global__ __launch_bounds__(kIcpThreads, KFX_ICP_MINB) void k_icp_track(IcpPlan
     }
     for (int it = 0; it < pl.iters[l] && !fail; ++it, ++slot) {
       unsigned long long *sh = sy->sums + (size_t)slot * kIcpShards * 27;
-      target += min(pl.groups[l], (int)gridDim.x);  // arrivals: the blocks with a group
-      (void)target;
-      {
+      {  // arrivals: the blocks with a group
         const int m = min(pl.groups[l], (int)gridDim.x), r = (int)(blockIdx.x & 7u);
         tsub += r < m ? (unsigned)((m - r + 7) / 8) : 0u;  // participants of residue r (blocks 0 .. m-1)
         ttop += (unsigned)min(m, 8);
@@ -1015,13 +972,12 @@ __global__ __launch_bounds__(kIcpThreads, KFX_ICP_MINB) void k_icp_track(IcpPlan
           if (threadIdx.x == 0 && !(withhold && slot == 0)) {
             // the last arriver releases the iteration: spinners poll 8 flag
             // copies instead of the contended arrival counter
-#if KFX_ICP_HIER
             // arrivals counted per residue b % 8 (one XCD each under the
             // round-robin placement; placement decides speed only): ~38
-            // atomics per counter instead of 300 on one, whose serialisation
-            // (~11 ns each) was ~1.7 us of every iteration's hand-off
-            // (tools/icp_barrier_bench.hip); a residue's last arriver adds to
-            // the top counter, whose last arriver releases
+            // atomics per counter instead of 300 on one flat counter, whose
+            // serialisation (~11 ns each) was ~1.7 us of every iteration's
+            // hand-off (tools/icp_barrier_bench.hip); a residue's
+            // last arriver adds to the top counter, whose last arriver releases
             const unsigned n = __hip_atomic_fetch_add(&sy->sub[blockIdx.x & 7u].v, 1u, __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_AGENT);
             if (n == tsub - 1) {
@@ -1031,14 +987,6 @@ __global__ __launch_bounds__(kIcpThreads, KFX_ICP_MINB) void k_icp_track(IcpPlan
                   __hip_atomic_store(&sy->release[k].v, (unsigned)(slot + 1), __ATOMIC_RELAXED,
                                      __HIP_MEMORY_SCOPE_AGENT);
             }
-#else
-            const unsigned n =
-                __hip_atomic_fetch_add(&sy->arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (n == target - 1)
-              for (int k = 0; k < 8; ++k)
-                __hip_atomic_store(&sy->release[k].v, (unsigned)(slot + 1), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-#endif
           }
         }
       }
@@ -1127,7 +1075,7 @@ __global__ __launch_bounds__(kIcpThreads, KFX_ICP_MINB) void k_icp_track(IcpPlan
     for (int i = threadIdx.x; i < n; i += kIcpThreads)
       __hip_atomic_store(&sy->sums[i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x == 0) {
-      __hip_atomic_store(&sy->arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&sy->rsv, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&sy->exit, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&sy->top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1541,7 +1489,7 @@ __device__ __forceinline__ void int_column(const VolView &v, const LevelGeom &g,
   }
 }
 
-// Occlusion clip of a column tile's intervals (KFX_INT_OCCL).  A voxel can
+// Occlusion clip of a column tile's intervals.  A voxel can
 // only be updated where its pixel's depth d satisfies d - il |vc| >= -trunc
 // (tsdf_volume.cu:67-71), and il |vc| >= vc.z / 1.0011 for every in-image
 // voxel, so no voxel with vc.z > (D + trunc) * 1.0011 is updated when D bounds
@@ -1554,16 +1502,13 @@ __device__ __forceinline__ void int_column(const VolView &v, const LevelGeom &g,
 // sphere) are then not visited at all; the result is unchanged (only voxels
 // that cannot pass are dropped).  Lanes' [zl, zh] and the union [wl, wh] are
 // tightened in place (wave-uniform control flow).
-#ifndef KFX_INT_OCCL
-#define KFX_INT_OCCL 1
-#endif
 #ifndef KFX_INT_OCCL_CELLS
 #define KFX_INT_OCCL_CELLS 64
 #endif
 constexpr int kOcclCells = KFX_INT_OCCL_CELLS;
 __device__ __forceinline__ void int_tile_clip(const VolView &v, const LevelGeom &g, const float2 *dl, f3 vc0, f3 zs,
                                               int lane, int &zl, int &zh, int &wl, int &wh) {
-  if (!KFX_INT_OCCL || wh < wl) return;
+  if (wh < wl) return;
   const bool own = zl <= zh;
   float umin = kInfF, umax = -kInfF, vmin = kInfF, vmax = -kInfF;
   bool bad = false;
@@ -1883,17 +1828,6 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
         }
       continue;
     }
-#if KFX_INT_BSKIP
-    // a batch in which no voxel of any lane passes (behind the surfaces, out
-    // of the image): no loads, update arithmetic or stores (wave-uniform)
-    bool anyok = false;
-#pragma unroll
-    for (int j = 0; j < kB; ++j) anyok = anyok | ok[j];
-    if (!__any(anyok)) {
-      iz += (Idx)kB * slice;
-      continue;
-    }
-#endif
     // tsdf/weight of the voxels that pass (issuing them with the depth
     // gathers, before the depth test, measured slower: the rejected voxels'
     // extra reads cost more than the saved round trip)
@@ -1906,13 +1840,12 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
       t0[j] = mem.ld_t(i);
       w0[j] = mem.ld_w(i);
     }
-#if KFX_INT_LDALL
-    // all kB voxels' loads issued together, one wait: the compiler otherwise
-    // sinks a voxel's loads into its update branch (the loaded values are
-    // only used there), which puts them on a round trip of their own
+    // all kB voxels' loads pinned here, issued together with one wait: the
+    // compiler otherwise sinks a voxel's loads into its update branch (the
+    // loaded values are only used there), which puts them on a round trip of
+    // their own (C2 -1.5 us)
 #pragma unroll
     for (int j = 0; j < kB; ++j) asm volatile("" ::"v"(t0[j]), "v"(w0[j]));
-#endif
     iz += (Idx)kB * slice;
     // The update arithmetic of all kB voxels, two voxels per packed op and
     // without branches (voxels that do not pass compute values nobody
@@ -2076,76 +2009,12 @@ __device__ __forceinline__ float interp32(const VolView &v, __amdgpu_buffer_rsrc
   return s;
 }
 
-// The 6 trilinear interpolations of compute_normal (kIdx32 volumes) with the
-// loads of kG interpolations in flight together (KFX_RAY_NG: 1 = one round trip
-// per interpolation, 6 = all 48 corner loads in one): the same corners,
-// weights and sum order as interp32.
-#ifndef KFX_RAY_NG
-#define KFX_RAY_NG 1
-#endif
-template <int kG>
-__device__ __forceinline__ f3 compute_normal_g(const VolView &v, const RayConsts &rc, f3 p) {
-  const __amdgpu_buffer_rsrc_t t = make_rsrc(v.tsdf, (unsigned)(2 * v.local_voxels()));
-  const unsigned col = (unsigned)v.zn << 6;
-  float f[6];
-#pragma unroll
-  for (int g0 = 0; g0 < 6; g0 += kG) {
-    int16_t raw[kG][8];
-    bool ok[kG];
-#pragma unroll
-    for (int q = 0; q < kG; ++q) {
-      const int k = g0 + q, ax = k >> 1;
-      const float sgn = (k & 1) ? -1.f : 1.f;
-      const f3 pq = {ax == 0 ? p.x + sgn * rc.gd.x : p.x, ax == 1 ? p.y + sgn * rc.gd.y : p.y,
-                     ax == 2 ? p.z + sgn * rc.gd.z : p.z};
-      const f3 cf = mulc(pq, rc.vs_inv);
-      const int gx = f2i_rd(cf.x), gy = f2i_rd(cf.y), gz = f2i_rd(cf.z);
-      ok[q] = !(gx < 0 || gx >= v.X - 1 || gy < 0 || gy >= v.Y - 1 || gz < 0 || gz >= v.Z - 1) &&
-              (unsigned)(gz - v.zb) < (unsigned)(v.zn - 1);
-      const unsigned tile = __umul24((unsigned)gy >> 3, (unsigned)v.tiles_x) + ((unsigned)gx >> 3);
-      const unsigned i0 = ok[q] ? (((tile * (unsigned)v.zn + (unsigned)(gz - v.zb)) << 6) |
-                                   (((unsigned)gy & 7u) << 3 | ((unsigned)gx & 7u)))
-                                : 0u;
-      const unsigned dx = (gx & 7) == 7 ? col - 7u : 1u;
-      const unsigned dy = (gy & 7) == 7 ? __umul24((unsigned)v.tiles_x, col) - 56u : 8u;
-      const unsigned o[8] = {i0, i0 + 64u, i0 + dy, i0 + dy + 64u, i0 + dx, i0 + dx + 64u, i0 + dx + dy,
-                             i0 + dx + dy + 64u};
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-        raw[q][c] = ok[q] ? (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, o[c] << 1, 0, 0) : (int16_t)0;
-    }
-#pragma unroll
-    for (int q = 0; q < kG; ++q) {
-      const int k = g0 + q, ax = k >> 1;
-      const float sgn = (k & 1) ? -1.f : 1.f;
-      const f3 pq = {ax == 0 ? p.x + sgn * rc.gd.x : p.x, ax == 1 ? p.y + sgn * rc.gd.y : p.y,
-                     ax == 2 ? p.z + sgn * rc.gd.z : p.z};
-      const f3 cf = mulc(pq, rc.vs_inv);
-      const int gx = f2i_rd(cf.x), gy = f2i_rd(cf.y), gz = f2i_rd(cf.z);
-      const float a = cf.x - (float)gx, b = cf.y - (float)gy, c = cf.z - (float)gz;
-      auto T = [&](int i) { return (float)raw[q][i] * kDivShortMax; };
-      float s = 0.f;
-      s += T(0) * (1 - a) * (1 - b) * (1 - c);
-      s += T(1) * (1 - a) * (1 - b) * c;
-      s += T(2) * (1 - a) * b * (1 - c);
-      s += T(3) * (1 - a) * b * c;
-      s += T(4) * a * (1 - b) * (1 - c);
-      s += T(5) * a * (1 - b) * c;
-      s += T(6) * a * b * (1 - c);
-      s += T(7) * a * b * c;
-      f[k] = ok[q] ? s : NAN;
-    }
-  }
-  f3 n;
-  n.x = (f[0] - f[1]) / rc.gd.x;
-  n.y = (f[2] - f[3]) / rc.gd.y;
-  n.z = (f[4] - f[5]) / rc.gd.z;
-  return normalized(n);
-}
-
+// kIdx32 volumes: each of the 6 trilinear interpolations is one round trip of
+// 8 corner loads (interp32); issuing the loads of two or six interpolations
+// before waiting spills registers at the raycast's occupancy budget
+// (DESIGN.md §4).
 template <bool kIdx32 = false>
 __device__ f3 compute_normal(const VolView &v, const RayConsts &rc, f3 p) {
-  if constexpr (kIdx32 && KFX_RAY_NG > 1) return compute_normal_g<KFX_RAY_NG>(v, rc, p);
   const __amdgpu_buffer_rsrc_t t = make_rsrc(v.tsdf, kIdx32 ? (unsigned)(2 * v.local_voxels()) : 0u);
   auto ip = [&](f3 q) { return kIdx32 ? interp32(v, t, mulc(q, rc.vs_inv)) : interp(v, mulc(q, rc.vs_inv)); };
   f3 n;
@@ -2225,12 +2094,6 @@ __device__ __forceinline__ float box_limit(int B, int bx, int by, int nbx, int n
 __device__ __forceinline__ f3 ff_add3(f3 p, f3 s, int n) {
   return {ff_add_fast(p.x, s.x, n), ff_add_fast(p.y, s.y, n), ff_add_fast(p.z, s.z, n)};
 }
-#ifndef KFX_RAY_EXIT
-#define KFX_RAY_EXIT 1  // a ray whose remaining samples all lie in a clear box ends there
-#endif
-#ifndef KFX_RAY_CHAIN
-#define KFX_RAY_CHAIN 2  // skip lookups: boxes per round trip (1 or 2)
-#endif
 // The brick box's lateral (x / y) exit from voxel position (cx, cy) in cell (bx, by).
 __device__ __forceinline__ float brick_lateral_exit(const VolView &v, int bx, int by, float cx, float cy, f3 dv, f3 idv) {
   const float xl = bx > 0 ? (float)(8 * bx - 8) : -kInf, xh = bx < v.tiles_x - 1 ? (float)(8 * bx + 15) : kInf;
@@ -2258,7 +2121,7 @@ __device__ __forceinline__ float run_box(const VolView &v, unsigned long long w,
 // Samples a ray may replay from voxel position (cx, cy, cz) (< 1: blocked).
 // The super-brick's box when its cell is clear (its 3x3 box contains the
 // brick's laterally; tools/raysim: the brick box alone adds < 1 % of lookups
-// there), else the brick's.  KFX_RAY_CHAIN 2: the words of the column at the
+// there), else the brick's.  Two boxes per round trip: the words of the column at the
 // brick box's lateral exit point (known before any word is back) are loaded
 // in the same round trip, and that column's brick box extends the run when
 // the point lies inside it (a ray along a tilted surface leaves the boxes
@@ -2273,7 +2136,6 @@ __device__ __forceinline__ float skip_limit(const VolView &v, float cx, float cy
   const int lsz = min(max((iz >> 5) - v.sz0, 0), v.nsz - 1);
   const unsigned long long bwd = v.bocc[(size_t)(by * v.tiles_x + bx) * v.bw + (lbz >> 6)];
   const uint32_t swd = v.socc[(size_t)(sy * v.stx + sx) * v.sw + (lsz >> 5)];
-#if KFX_RAY_CHAIN >= 2
   const float t1r = brick_lateral_exit(v, bx, by, cx, cy, dv, idv);
   const float t1 = t1r < 1.0e6f ? t1r : 0.f;  // (no lateral exit: the same column, unused)
   const float c1x = cx + t1 * dv.x, c1y = cy + t1 * dv.y, c1z = cz + t1 * dv.z;
@@ -2281,7 +2143,6 @@ __device__ __forceinline__ float skip_limit(const VolView &v, float cx, float cy
   const int bx1 = min(max(ix1 >> 3, 0), v.tiles_x - 1), by1 = min(max(iy1 >> 3, 0), v.tiles_y - 1);
   const int lbz1 = min(max((iz1 >> 3) - v.bz0, 0), v.nbz - 1);
   const unsigned long long bwd1 = v.bocc[(size_t)(by1 * v.tiles_x + bx1) * v.bw + (lbz1 >> 6)];
-#endif
   const int bb = lbz & 63, sb = lsz & 31;
   const bool sclear = !((swd >> sb) & 1u), bclear = !((bwd >> bb) & 1ull);
   float lim = 0.f;
@@ -2289,14 +2150,12 @@ __device__ __forceinline__ float skip_limit(const VolView &v, float cx, float cy
     lim = run_box(v, sclear ? (unsigned long long)swd : bwd, sclear ? 32 : 64, sclear ? sb : bb, sclear ? lsz : lbz,
                   sclear ? v.nsz : v.nbz, sclear ? v.sz0 : v.bz0, sclear ? 32 : 8, sclear ? sx : bx, sclear ? sy : by,
                   sclear ? v.stx : v.tiles_x, sclear ? v.sty : v.tiles_y, cx, cy, cz, dv, idv);
-#if KFX_RAY_CHAIN >= 2
     const int bb1 = lbz1 & 63;
     if (t1 > 0.f && t1 <= lim && !((bwd1 >> bb1) & 1ull)) {
       const float lim1 = run_box(v, bwd1, 64, bb1, lbz1, v.nbz, v.bz0, 8, bx1, by1, v.tiles_x, v.tiles_y, c1x, c1y, c1z,
                                  dv, idv);
       if (lim1 >= 1.f) lim = fmaxf(lim, t1 + lim1);
     }
-#endif
   }
   return lim;
 }
@@ -2334,8 +2193,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
   const float *pose_src = xpose ? xpose : st->ray_c2v.R;  // R[9], t[3] (+ Rinv[9] in xpose)
   const int skind = xpose ? 1 : st->ray_kind;
   const size_t wave_id = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const unsigned long long t_wave0 = KFX_RAY_HINT ? __builtin_amdgcn_s_memtime() : 0ull;
-  if (KFX_RAY_HINT && !kSlab && !kStats && v.rdur) {
+  const unsigned long long t_wave0 = __builtin_amdgcn_s_memtime();
+  if (!kSlab && !kStats && v.rdur) {
     const unsigned d = __builtin_amdgcn_readfirstlane(v.rdur[wave_id]);
     if (d >= KFX_RAY_HINT_T0 * 7 / 4) __builtin_amdgcn_s_setprio(3);
     else if (d >= KFX_RAY_HINT_T0 * 11 / 8) __builtin_amdgcn_s_setprio(2);
@@ -2415,7 +2274,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
     constexpr int kR = KFX_RAY_KR;
     int sprev = isnan(tprev) ? 0 : (tprev > 0.f ? 1 : (tprev < 0.f ? -1 : 0));
     uint32_t kbase = 1u;  // loop sample index of the batch's first sample
-#if KFX_RAY_SLAB_SKIP
     if (kSlab && live) {
       // A slab stores slices [zb, zb + zn): the samples a ray takes before it
       // reaches them read no voxel (NaN: no event, tsdf_volume.cu:184-188), so
@@ -2443,7 +2301,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
         }
       }
     }
-#endif
     const RayMem<kIdx32> mem(v);
     // voxel validity 1 <= i <= dim-2 (tsdf_volume.cu:184-185) tested on the
     // rounded floats (exact integers; NaN fails like __float2int_rn's INT_MIN)
@@ -2503,7 +2360,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
             if (kStats) st_blocked += 1;
             break;
           }
-#if KFX_RAY_EXIT
           if (!kSlab && (tfar - ray_len) * rstep + 2.f <= fminf(lim, rc.skip_cap)) {
             // every sample the loop has left (at most (tfar - ray_len) / step
             // + 1, 2 of margin over the accumulated rounding) lies in the
@@ -2513,7 +2369,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
             live = false;
             break;
           }
-#endif
           int n = (int)fminf(lim, rc.skip_cap);
           if (kSlab) {
             // a slab's ray ends 2 slices past its owned range (no owned
@@ -2720,7 +2575,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
 #endif
     if (cand) {  // the wave's normal pass
       cand = false;
-      const f3 n = compute_normal<kIdx32 && KFX_RAY_N32>(v, rc, cvert);
+      // (kIdx32 volumes: 32-bit tile-column offsets + buffer loads)
+      const f3 n = compute_normal<kIdx32>(v, rc, cvert);
       if (!isnan(n.x * n.y * n.z)) {
         // Rinv read here (scalar loads of the uniform pose; the transpose of
         // cam2vol's R, or the stage seam's explicit Rinv)
@@ -2777,7 +2633,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
     }
     return;
   }
-  if (KFX_RAY_HINT && !kSlab && !kStats && v.rdur && (threadIdx.x & 63) == 0)
+  if (!kSlab && !kStats && v.rdur && (threadIdx.x & 63) == 0)
     v.rdur[wave_id] = (unsigned)((__builtin_amdgcn_s_memtime() - t_wave0) >> 10);
   if (act) {
     if (kSlab) {  // key, pend + payload {Ts, nout} (kfx_internal.h slab combine)
@@ -3245,7 +3101,7 @@ __global__ __launch_bounds__(256) void k_xsweep(VolView v, DevPose aff, int zlo,
   const size_t ubase = (size_t)blockIdx.y * ntiles;  // unit index = ubase + tile
   const int tl = T0 + lane;
   const bool mine = lane < K && tl < ntiles;
-  const bool have = mine && !(KFX_EXTRACT_SKIP && brick_clear(v, tl, c0));
+  const bool have = mine && !brick_clear(v, tl, c0);  // waves of clear bricks read nothing
   if (kMode != kXEmit && mine && !have) counts[ubase + tl] = 0u;
   unsigned long long work = __ballot(have);
   while (work) {  // wave-uniform

@@ -59,19 +59,28 @@ def test_create_rejects_bad_arguments(kfx_lib):
 
 def test_product_build_refuses_experiment_macros():
     """make ARCH=gfx950 with -DKFX_* macros is refused for the product library
-    (experiments build into lib/var_<name>), and the shipped kernel source holds
-    none of the dropped experiment switches."""
+    (experiments build into lib/var_<name>), and the shipped library source
+    holds none of the dropped experiment switches."""
     import subprocess
     pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "slam-kinectfusion_amd")
     r = subprocess.run(["make", "-n", "-C", pkg, "ARCH=gfx950", "EXTRA=-DKFX_INT_CERT=1"],
                        capture_output=True, text=True)
     assert r.returncode != 0 and "var_" in (r.stdout + r.stderr)
-    src = open(os.path.join(pkg, "csrc", "kfx_kernels.hip")).read()
+    src = "".join(open(os.path.join(pkg, "csrc", f)).read()
+                  for f in ("kfx_kernels.hip", "kfx_api.hip", "kfx_internal.h"))
     for m in ("KFX_INT_ZCLASS", "KFX_INT_CERT", "KFX_INT_DEDUP", "KFX_INT_LEAN", "KFX_INT_PLAN", "KFX_INT_PRIO",
               "KFX_RAY_PRIO", "KFX_ICP_XCOARSE", "KFX_INT_EXP", "KFX_PLAN_EXP", "KFX_RAY_NOREPLAY",
               "KFX_RAY_NONORMAL", "KFX_RAY_PIPE", "KFX_RAY_FFREPLAY", "KFX_RAY_FF_MIN", "KFX_RAY_FAKE_REPLAY",
               "KFX_RAY_LDS", "wrong values"):
         assert m not in src, m
+    # settled A/B switches: the shipped source has only the side that was kept
+    # (whole names: the tunables KFX_RAY_HINT_T0 and KFX_INT_OCCL_CELLS stay)
+    import re
+    for m in ("KFX_INT_PK", "KFX_INT_BSKIP", "KFX_INT_LDALL", "KFX_INT_OCCL", "KFX_ICP_HIER", "KFX_ICP_XCD",
+              "KFX_RAY_NG", "KFX_RAY_N32", "KFX_RAY_EXIT", "KFX_RAY_CHAIN", "KFX_RAY_SLAB_SKIP", "KFX_RAY_HINT",
+              "KFX_EXTRACT_SKIP", "KFX_PREP_AFTER_ICP", "KFX_PREP_AFTER_INT", "KFX_PREP_SIG", "KFX_ORDER_OFF_PATH",
+              "KFX_FREE_ELIDE"):
+        assert not re.search(r"\b" + m + r"\b", src), m
 
 
 def test_adapter_header_compiles_and_links(tmp_path):

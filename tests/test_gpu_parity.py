@@ -497,6 +497,70 @@ def test_pipeline_modes_and_inputs_identical(seq_qvga):
             assert np.array_equal(a, b)
 
 
+def test_overlapped_frames_deep_volume_identical(seq_qvga):
+    """Overlapped frames on a 128 x 128 x 1024 volume (16 mm voxels, 16.384 m
+    deep): the smallest shape whose integrate orders its tiles by length
+    (1024 <= zn < 2048), so the cross-stream k_int_order really rewrites the
+    tile order between frames (256 tiles x 4 chunks).  Staged, mixed and
+    pinned-ring frames, with the raycast start signal and with the event path,
+    give the single-stream pipeline's poses, volume and model maps bit for bit.
+
+    Limits: any permutation of the tiles integrates the same volume, so this
+    catches a corrupted or half-rewritten order, and wrong arguments or stale
+    state after a mode change; it does not catch a missing wait whose window is
+    narrow."""
+    bgr, dep, gt = seq_qvga
+    intr = synth.Intrinsics.qvga()
+    depf = dep.astype(np.float32)
+
+    def make_deep(signal=True):
+        p = default_params(dims=128, range_m=L_VOL)
+        p.volu_dims[2] = 1024
+        p.volu_range[2] = 16.384
+        if not signal:  # overlapped frames ordered by events, not the raycast start signal
+            os.environ["KFX_STREAM_SIGNAL"] = "0"
+        try:
+            return KinectFusion(Intrinsics.from_any(intr), p)
+        finally:
+            os.environ.pop("KFX_STREAM_SIGNAL", None)
+
+    def result(kf):
+        maps = [kf.frame_maps(KFX_FRAME_PREV, l)[1:] for l in range(3)]
+        r = (kf.pose_record, kf.volume_soa(), maps)
+        kf.close()
+        return r
+
+    kf = make_deep()
+    assert _run_pipeline(kf, bgr, dep) == [KFX_OK] * len(dep)
+    ref = result(kf)
+    assert ref[0].shape == (len(dep), 4, 4)  # every frame tracked
+
+    for mode in ("staged", "staged_events", "staged_mixed_back", "async", "async_events"):
+        kf = make_deep(signal=not mode.endswith("_events"))
+        if mode == "staged_mixed_back":  # overlapped, single-stream, overlapped again
+            kf.stage_frames(bgr, depf)
+            for k in range(3):
+                kf.pipeline_staged(k)  # raises unless KFX_OK
+            for k in range(3, 6):
+                assert kf.pipeline(bgr[k], depf[k]) == KFX_OK
+            for k in range(6, len(dep)):
+                kf.pipeline_staged(k)
+        elif mode.startswith("staged"):
+            kf.stage_frames(bgr, depf)
+            for k in range(len(dep)):
+                kf.pipeline_staged(k)
+        else:  # pipelined host input through the pinned ring
+            for k in range(len(dep)):
+                kf.pipeline_async(bgr[k], depf[k])  # raises unless KFX_OK
+        assert kf.synchronize() == KFX_OK, mode
+        poses, vol, maps = result(kf)
+        assert np.array_equal(poses, ref[0]), mode
+        for a, b in zip(vol, ref[1]):
+            assert np.array_equal(a, b), mode
+        for (gv, gn), (rv, rn) in zip(maps, ref[2]):
+            assert feq(gv, rv) and feq(gn, rn), mode
+
+
 def test_icp_watchdog_stall_switches_to_cooperative_launch(seq_qvga):
     """A persistent-ICP grid barrier that never completes (test hook: block 0
     withholds its first arrival) fires the watchdog: that frame reports an
