@@ -356,6 +356,42 @@ int kfx_extract_mesh(kfx_ctx *ctx, float *tri_xyz, int64_t cap_tris, int64_t *n_
 /* ASCII PLY of a triangle soup: 3n vertices (%g), n faces "3 i j k". */
 int kfx_write_ply_mesh(const char *path, const float *tri_xyz, int64_t n_tris);
 
+/* Attributed extraction (an extension: the reference fuses colour into the
+ * volume, tsdf_volume.cu:82-95, and never reads it back).  Item i of an _attr
+ * call is item i of the plain call (same canonical order, total, cap prefix
+ * and slab concatenation; x, y, z are the plain call's bits), with a unit
+ * normal and the fused colour.  A vertex lies on the grid edge from voxel a to
+ * b = a + e_axis.
+ *   colour (integers): ta = |tsdf_a|, tb = |tsdf_b| (raw int16), ca, cb the
+ *     24-bit packed colours, 0 = never coloured.  Both coloured: channel j =
+ *     (ca_j*tb + cb_j*ta + ((ta+tb)>>1)) / (ta+tb), a = 255; one coloured: that
+ *     colour, a = 255; none: 0,0,0 and a = 0.  b, g, r = the volume's c0, c1,
+ *     c2 (the BGR order of the input images).
+ *   normal (float32, no contraction): g_k(q) = (hi - lo) / voxel_size[k] with
+ *     hi / lo = F at q +/- e_k where that voxel lies in the volume and has
+ *     weight != 0, else F(q), and the difference doubled when exactly one of
+ *     the two is valid; m = g(a)*|F_b| + g(b)*|F_a|; n = normalize(R_volume m)
+ *     (0,0,0 when the length is 0).  The TSDF is positive in front of the
+ *     surface: normals point out of it.
+ * cap = 0 (or a null buffer with cap 0) counts only; kfx_set_extract_passes,
+ * kfx_get_extract_passes and kfx_get_extract_ms apply as to the plain calls. */
+typedef struct kfx_vertex {
+  float x, y, z;
+  float nx, ny, nz;
+  uint8_t b, g, r, a;
+} kfx_vertex; /* 28 bytes */
+int kfx_extract_points_attr(kfx_ctx *ctx, kfx_vertex *out, int64_t cap, int64_t *n_points);
+/* 3 kfx_vertex per triangle */
+int kfx_extract_mesh_attr(kfx_ctx *ctx, kfx_vertex *out, int64_t cap_tris, int64_t *n_tris);
+/* ASCII PLY: "property float x y z nx ny nz", "property uchar red green blue";
+ * lines "%g %g %g %g %g %g %d %d %d" (red = r).  The mesh file adds the face
+ * element of kfx_write_ply_mesh (faces "3 3i 3i+1 3i+2"). */
+int kfx_write_ply_attr(const char *path, const kfx_vertex *v, int64_t n);
+int kfx_write_ply_mesh_attr(const char *path, const kfx_vertex *v, int64_t n_tris);
+/* extract (cap <= 0: KFX_DEFAULT_CLOUD_POINTS items) + write */
+int kfx_save_pointcloud_attr(kfx_ctx *ctx, const char *path, int64_t cap);
+int kfx_save_mesh_attr(kfx_ctx *ctx, const char *path, int64_t cap_tris);
+
 /* ---- dataset front-end (host only; no GPU needed) --------------------------
  * depth_sensor in its DATASET build (depth_sensor.cpp:11-46 open, :186-196
  * getFrame) without OpenCV: the PNG files of `<dir>/color` and `<dir>/depth` in

@@ -167,6 +167,15 @@ class kinectfusion {
     kfx_write_ply(path.c_str(), points_array_.empty() ? nullptr : points_array_.ptr<float>(),
                   points_array_.cols);
   }
+  // Extensions with no reference counterpart (the reference fuses colour into
+  // the volume and never reads it back): ASCII PLY of the zero-crossing cloud /
+  // the marching-cubes mesh with a unit normal and the fused colour per vertex.
+  void saveColoredPointcloud(std::string path) {
+    if (kfx_save_pointcloud_attr(ctx_, path.c_str(), 0) != KFX_OK) throw std::runtime_error(kfx_last_error());
+  }
+  void saveColoredMesh(std::string path) {
+    if (kfx_save_mesh_attr(ctx_, path.c_str(), 0) != KFX_OK) throw std::runtime_error(kfx_last_error());
+  }
   cv::Affine3f getCurCameraPose() { return pose_record.back(); }
   void release() {
     if (ctx_) kfx_destroy(ctx_);

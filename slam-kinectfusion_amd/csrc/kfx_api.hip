@@ -2220,10 +2220,14 @@ int kfx_get_extract_ms(kfx_ctx *c, float out_ms[3]) {
 // two-pass path writes the first cap items instead.  Not taken (returns 0)
 // for a count-only call (cap = 0), with kfx_set_extract_passes(2), or when
 // the buffers cannot be allocated: the caller then runs the two-pass path.
-// per = floats per item (3 per point, 9 per triangle).
+// per = 32-bit words per item (3 per point, 9 per triangle; attributed: 7 / 21).
 constexpr int64_t kExtractPoolItems = (int64_t)1 << 23;  // single-pass pool: <= 8.4 M items (100 MB of points)
+// words per item: kfx_vertex is 7 words (kfx_kernels.hip kVertexWords)
+static_assert(sizeof(kfx_vertex) == 28, "kfx_vertex is 7 32-bit words");
+static int extract_item_words(bool mesh, bool attr) { return (mesh ? 3 : 1) * (attr ? 7 : 3); }
 static int extract_single_pass(kfx_ctx *c, const uint8_t *tab, int zlo, int zhi, float *host, int64_t cap,
-                               int per, int64_t *total_out) {
+                               bool attr, int64_t *total_out) {
+  const int per = extract_item_words(tab != nullptr, attr);
   if (cap <= 0 || cap > (int64_t)1 << 36 || c->extract_mode == 2) return 0;
   const size_t waves = extract_waves(c->vol, zlo, zhi);
   if (waves == 0) return 0;
@@ -2237,7 +2241,10 @@ static int extract_single_pass(kfx_ctx *c, const uint8_t *tab, int zlo, int zhi,
   // caller's cap (a larger result overflows it and takes the emit pass: the
   // counts are complete either way); the ordered output is allocated once
   // the count is known (n = min(total, cap) items, not cap)
-  const int64_t pool_cap = std::min<int64_t>(cap, kExtractPoolItems);
+  // An attributed call's pool has the plain call's bytes, not its item count
+  // (3/7 of the items): a 2048^3 call allocates what it did before.
+  const int64_t pool_cap =
+      std::min<int64_t>(cap, kExtractPoolItems * extract_item_words(tab != nullptr, false) / per);
   if (hipMalloc(&ws, wsb) != hipSuccess || hipMalloc(&pool, (size_t)pool_cap * per * sizeof(float)) != hipSuccess) {
     (void)hipGetLastError();
     if (ws) (void)hipFree(ws);
@@ -2255,7 +2262,7 @@ static int extract_single_pass(kfx_ctx *c, const uint8_t *tab, int zlo, int zhi,
   if (e == hipSuccess && extract_events(c) == KFX_OK) {
     (void)hipEventRecord(c->xev[0], c->stream);
     launch_extract_pool(c->stream, c->vol, vp, zlo, zhi, tab, counts, misc + 1, pool_at, list, pool,
-                        (unsigned long long)pool_cap, (unsigned *)(misc + 2));
+                        (unsigned long long)pool_cap, (unsigned *)(misc + 2), attr);
     (void)hipEventRecord(c->xev[1], c->stream);
     launch_scan(c->stream, counts, offsets, bsum, waves, misc);
     (void)hipEventRecord(c->xev[2], c->stream);
@@ -2272,9 +2279,9 @@ static int extract_single_pass(kfx_ctx *c, const uint8_t *tab, int zlo, int zhi,
         launch_extract_copy(c->stream, list, (unsigned)(h[1] >> 40), counts, pool_at, offsets, pool, dout,
                             (unsigned long long)n, per);
       else if (tab)
-        launch_mesh(c->stream, c->vol, vp, zlo, zhi, tab, counts, offsets, dout, (unsigned long long)n);
+        launch_mesh(c->stream, c->vol, vp, zlo, zhi, tab, counts, offsets, dout, (unsigned long long)n, attr);
       else
-        launch_extract(c->stream, c->vol, vp, zlo, zhi, counts, offsets, dout, (unsigned long long)n);
+        launch_extract(c->stream, c->vol, vp, zlo, zhi, counts, offsets, dout, (unsigned long long)n, attr);
       (void)hipEventRecord(c->xev[4], c->stream);
       e = hipGetLastError();
       if (e == hipSuccess) e = hipMemcpyAsync(host, dout, (size_t)n * per * sizeof(float), hipMemcpyDeviceToHost, c->stream);
@@ -2297,17 +2304,30 @@ static int extract_single_pass(kfx_ctx *c, const uint8_t *tab, int zlo, int zhi,
   return done;
 }
 
-int kfx_extract_points(kfx_ctx *c, float *xyz, int64_t cap, int64_t *n_points) {
+static void build_mc_table(uint8_t tab[256 * 16]);
+
+// kfx_extract_points / kfx_extract_mesh and their _attr forms: `out` holds cap
+// items of extract_item_words(mesh, attr) 32-bit words.
+static int extract_items(kfx_ctx *c, bool mesh, bool attr, void *out, int64_t cap, int64_t *n_items) {
   int r = check_ctx(c);
   if (r) return r;
-  if (cap < 0 || (cap > 0 && !xyz)) return set_err(KFX_ERR_ARG, "bad point buffer");
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, mesh ? "bad triangle buffer" : "bad point buffer");
   HIPCHK(hipStreamSynchronize(c->stream));
-  // FullScan6 visits z = 0 .. Z-2 (it reads z + 1); a slab its owned part
+  if (mesh && !c->mc_tab) {
+    uint8_t tab[256 * 16];
+    build_mc_table(tab);
+    if ((r = dalloc(c, (void **)&c->mc_tab, sizeof(tab)))) return r;
+    HIPCHK(hipMemcpy(c->mc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+  }
+  const uint8_t *tab = mesh ? c->mc_tab : nullptr;
+  const size_t item = (size_t)extract_item_words(mesh, attr) * 4;
+  // FullScan6 visits z = 0 .. Z-2 (it reads z + 1), as do the cubes z .. z+1;
+  // a slab its owned part
   const int zlo = std::max(0, c->vol.own0), zhi = std::min(c->vol.own1, c->vol.Z - 1);
   const size_t waves = extract_waves(c->vol, zlo, zhi);
   int64_t total = 0;
-  if (waves > 0 && extract_single_pass(c, nullptr, zlo, zhi, xyz, cap, 3, &total)) {
-    if (n_points) *n_points = total;
+  if (waves > 0 && extract_single_pass(c, tab, zlo, zhi, (float *)out, cap, attr, &total)) {
+    if (n_items) *n_items = total;
     return KFX_OK;
   }
   c->extract_passes = 2;
@@ -2321,9 +2341,15 @@ int kfx_extract_points(kfx_ctx *c, float *xyz, int64_t cap, int64_t *n_points) {
     unsigned long long *bsum = offsets + waves;
     unsigned long long *dtot = bsum + nb;
     const DevPose vp = to_dev(c->p.volu_pose);
+    auto pass = [&](const unsigned long long *offs, float *dst, unsigned long long n) {
+      if (mesh)
+        launch_mesh(c->stream, c->vol, vp, zlo, zhi, tab, counts, offs, dst, n, attr);
+      else
+        launch_extract(c->stream, c->vol, vp, zlo, zhi, counts, offs, dst, n, attr);
+    };
     if ((r = extract_events(c))) return r;
     HIPCHK(hipEventRecord(c->xev[0], c->stream));
-    launch_extract(c->stream, c->vol, vp, zlo, zhi, counts, nullptr, nullptr, 0);
+    pass(nullptr, nullptr, 0);
     HIPCHK(hipEventRecord(c->xev[1], c->stream));
     launch_scan(c->stream, counts, offsets, bsum, waves, dtot);
     HIPCHK(hipEventRecord(c->xev[2], c->stream));
@@ -2335,13 +2361,12 @@ int kfx_extract_points(kfx_ctx *c, float *xyz, int64_t cap, int64_t *n_points) {
     float *dout = nullptr;
     c->extract_ms[2] = 0.f;
     if (e == hipSuccess && n > 0) {
-      e = hipMalloc(&dout, (size_t)n * 12);
+      e = hipMalloc(&dout, (size_t)n * item);
       if (e == hipSuccess) {
         (void)hipEventRecord(c->xev[3], c->stream);
-        launch_extract(c->stream, c->vol, vp, zlo, zhi, counts, offsets, dout,
-                       (unsigned long long)n);
+        pass(offsets, dout, (unsigned long long)n);
         (void)hipEventRecord(c->xev[4], c->stream);
-        e = hipMemcpyAsync(xyz, dout, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream);
+        e = hipMemcpyAsync(out, dout, (size_t)n * item, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) (void)hipEventElapsedTime(&c->extract_ms[2], c->xev[3], c->xev[4]);
         (void)hipFree(dout);
@@ -2350,10 +2375,18 @@ int kfx_extract_points(kfx_ctx *c, float *xyz, int64_t cap, int64_t *n_points) {
     (void)hipEventElapsedTime(&c->extract_ms[0], c->xev[0], c->xev[1]);
     (void)hipEventElapsedTime(&c->extract_ms[1], c->xev[1], c->xev[2]);
     (void)hipFree(ws);
-    if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("extract_points: ") + hipGetErrorString(e));
+    if (e != hipSuccess)
+      return set_err(KFX_ERR_HIP, std::string(mesh ? "extract_mesh: " : "extract_points: ") + hipGetErrorString(e));
   }
-  if (n_points) *n_points = total;
+  if (n_items) *n_items = total;
   return KFX_OK;
+}
+
+int kfx_extract_points(kfx_ctx *c, float *xyz, int64_t cap, int64_t *n_points) {
+  return extract_items(c, false, false, xyz, cap, n_points);
+}
+int kfx_extract_points_attr(kfx_ctx *c, kfx_vertex *out, int64_t cap, int64_t *n_points) {
+  return extract_items(c, false, true, out, cap, n_points);
 }
 
 // Marching-cubes triangle table, derived instead of typed in: for each of the
@@ -2422,66 +2455,10 @@ static void build_mc_table(uint8_t tab[256 * 16]) {
 }
 
 int kfx_extract_mesh(kfx_ctx *c, float *tri_xyz, int64_t cap, int64_t *n_tris) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (cap < 0 || (cap > 0 && !tri_xyz)) return set_err(KFX_ERR_ARG, "bad triangle buffer");
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (!c->mc_tab) {
-    uint8_t tab[256 * 16];
-    build_mc_table(tab);
-    if ((r = dalloc(c, (void **)&c->mc_tab, sizeof(tab)))) return r;
-    HIPCHK(hipMemcpy(c->mc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-  }
-  // cubes z .. z+1 for z in the owned slices below Z-1
-  const int zlo = std::max(0, c->vol.own0), zhi = std::min(c->vol.own1, c->vol.Z - 1);
-  const size_t waves = extract_waves(c->vol, zlo, zhi);
-  int64_t total = 0;
-  if (waves > 0 && extract_single_pass(c, c->mc_tab, zlo, zhi, tri_xyz, cap, 9, &total)) {
-    if (n_tris) *n_tris = total;
-    return KFX_OK;
-  }
-  c->extract_passes = 2;
-  if (waves > 0) {
-    const size_t nb = scan_blocks(waves);
-    char *ws = nullptr;
-    HIPCHK(hipMalloc(&ws, waves * 4 + waves * 8 + nb * 8 + 64));
-    unsigned *counts = (unsigned *)ws;
-    unsigned long long *offsets = (unsigned long long *)(ws + ((waves * 4 + 7) & ~(size_t)7));
-    unsigned long long *bsum = offsets + waves;
-    unsigned long long *dtot = bsum + nb;
-    const DevPose vp = to_dev(c->p.volu_pose);
-    if ((r = extract_events(c))) return r;
-    HIPCHK(hipEventRecord(c->xev[0], c->stream));
-    launch_mesh(c->stream, c->vol, vp, zlo, zhi, c->mc_tab, counts, nullptr, nullptr, 0);
-    HIPCHK(hipEventRecord(c->xev[1], c->stream));
-    launch_scan(c->stream, counts, offsets, bsum, waves, dtot);
-    HIPCHK(hipEventRecord(c->xev[2], c->stream));
-    unsigned long long ht = 0;
-    hipError_t e = hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    total = (int64_t)ht;
-    const int64_t n = std::min<int64_t>(total, cap);
-    float *dout = nullptr;
-    c->extract_ms[2] = 0.f;
-    if (e == hipSuccess && n > 0) {
-      e = hipMalloc(&dout, (size_t)n * 36);
-      if (e == hipSuccess) {
-        (void)hipEventRecord(c->xev[3], c->stream);
-        launch_mesh(c->stream, c->vol, vp, zlo, zhi, c->mc_tab, counts, offsets, dout, (unsigned long long)n);
-        (void)hipEventRecord(c->xev[4], c->stream);
-        e = hipMemcpyAsync(tri_xyz, dout, (size_t)n * 36, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) (void)hipEventElapsedTime(&c->extract_ms[2], c->xev[3], c->xev[4]);
-        (void)hipFree(dout);
-      }
-    }
-    (void)hipEventElapsedTime(&c->extract_ms[0], c->xev[0], c->xev[1]);
-    (void)hipEventElapsedTime(&c->extract_ms[1], c->xev[1], c->xev[2]);
-    (void)hipFree(ws);
-    if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("extract_mesh: ") + hipGetErrorString(e));
-  }
-  if (n_tris) *n_tris = total;
-  return KFX_OK;
+  return extract_items(c, true, false, tri_xyz, cap, n_tris);
+}
+int kfx_extract_mesh_attr(kfx_ctx *c, kfx_vertex *out, int64_t cap, int64_t *n_tris) {
+  return extract_items(c, true, true, out, cap, n_tris);
 }
 
 int kfx_write_ply_mesh(const char *path, const float *tri_xyz, int64_t n) {
@@ -2523,6 +2500,55 @@ int kfx_save_pointcloud(kfx_ctx *c, const char *path, int64_t cap) {
   if (n > 0 && (r = kfx_extract_points(c, pts.data(), n, &total))) return r;
   return kfx_write_ply(path, pts.data(), n);
 }
+
+// x y z nx ny nz red green blue per vertex (n_verts of them), after the header
+static void ply_attr_vertices(FILE *f, const kfx_vertex *v, int64_t n_verts) {
+  for (int64_t i = 0; i < n_verts; ++i)
+    std::fprintf(f, "%g %g %g %g %g %g %d %d %d\n", v[i].x, v[i].y, v[i].z, v[i].nx, v[i].ny, v[i].nz, (int)v[i].r,
+                 (int)v[i].g, (int)v[i].b);
+}
+static const char kPlyAttrProps[] =
+    "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
+    "property float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n";
+
+int kfx_write_ply_attr(const char *path, const kfx_vertex *v, int64_t n) {
+  if (!path || n < 0 || (n > 0 && !v)) return set_err(KFX_ERR_ARG, "bad argument");
+  FILE *f = std::fopen(path, "w");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\n%send_header\n", (long long)n, kPlyAttrProps);
+  ply_attr_vertices(f, v, n);
+  std::fclose(f);
+  return KFX_OK;
+}
+
+int kfx_write_ply_mesh_attr(const char *path, const kfx_vertex *v, int64_t n) {
+  if (!path || n < 0 || (n > 0 && !v)) return set_err(KFX_ERR_ARG, "bad argument");
+  FILE *f = std::fopen(path, "w");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\n%s"
+               "element face %lld\nproperty list uchar int vertex_indices\nend_header\n",
+               (long long)(3 * n), kPlyAttrProps, (long long)n);
+  ply_attr_vertices(f, v, 3 * n);
+  for (int64_t i = 0; i < n; ++i)
+    std::fprintf(f, "3 %lld %lld %lld\n", (long long)(3 * i), (long long)(3 * i + 1), (long long)(3 * i + 2));
+  std::fclose(f);
+  return KFX_OK;
+}
+
+// count, then extract min(total, cap) items and write them
+static int save_attr(kfx_ctx *c, const char *path, int64_t cap, bool mesh) {
+  if (!path) return set_err(KFX_ERR_ARG, "null path");
+  if (cap <= 0) cap = KFX_DEFAULT_CLOUD_POINTS;
+  int64_t total = 0;
+  int r = extract_items(c, mesh, true, nullptr, 0, &total);
+  if (r) return r;
+  const int64_t n = std::min(total, cap);
+  std::vector<kfx_vertex> v((size_t)n * (mesh ? 3 : 1));
+  if (n > 0 && (r = extract_items(c, mesh, true, v.data(), n, &total))) return r;
+  return mesh ? kfx_write_ply_mesh_attr(path, v.data(), n) : kfx_write_ply_attr(path, v.data(), n);
+}
+int kfx_save_pointcloud_attr(kfx_ctx *c, const char *path, int64_t cap) { return save_attr(c, path, cap, false); }
+int kfx_save_mesh_attr(kfx_ctx *c, const char *path, int64_t cap) { return save_attr(c, path, cap, true); }
 
 // ---- Z-slab sharding -------------------------------------------------------
 

@@ -309,21 +309,24 @@ void launch_inv_lambda(hipStream_t s, LevelGeom g0, float *inv_lambda);
 void launch_host_fetch(hipStream_t s, const void *src0, void *dst0, size_t n0, const void *src1, void *dst1,
                        size_t n1);
 // point extraction (FullScan6) over global slices [zlo, zhi): offsets == null
-// counts points per wave, else writes them (float3) at offsets (< cap)
+// counts points per wave, else writes them (float3) at offsets (< cap).
+// attr (here and below): attributed items of 7 32-bit words per vertex
+// (kfx_vertex: position, normal, colour) in place of float3 vertices
 size_t extract_waves(const VolView &v, int zlo, int zhi);
 void launch_extract(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi,
                     unsigned *counts, const unsigned long long *offsets, float *out,
-                    unsigned long long cap);
+                    unsigned long long cap, bool attr = false);
 // marching cubes over z in [zlo, zhi) (same waves / chunks as launch_extract);
 // tab: 256 x 16 bytes {n_tri, 3*n_tri edge indices}
 void launch_mesh(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
-                 unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap);
+                 unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap,
+                 bool attr = false);
 size_t scan_blocks(size_t n);  // bsum entries launch_scan needs (<= 65536)
 // one-read extraction (k_extract_pool + scan + k_extract_copy): tab = null
 // for points, the marching-cubes table for triangles
 void launch_extract_pool(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
                          unsigned *counts, unsigned long long *ctr, unsigned long long *pool_at, unsigned *list,
-                         float *pool, unsigned long long pool_cap, unsigned *overflow);
+                         float *pool, unsigned long long pool_cap, unsigned *overflow, bool attr = false);
 void launch_extract_copy(hipStream_t s, const unsigned *list, unsigned nlist, const unsigned *counts,
                          const unsigned long long *pool_at, const unsigned long long *offsets, const float *pool,
                          float *out, unsigned long long cap, int per);

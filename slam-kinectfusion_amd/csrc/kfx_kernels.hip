@@ -2907,8 +2907,84 @@ __global__ void k_group_reduce(GroupBufs in, GroupBufs out, size_t count, int is
 // per wave, a scan turns counts into offsets, pass 2 writes.
 constexpr int kExtractZ = 8;
 
+// ---- vertex attributes (kfx_extract_points_attr / kfx_extract_mesh_attr,
+// definitions: include/kfx.h) --------------------------------------
+// Gradient of F at voxel q = (x, y, z) (Fq = F(q)): per axis the difference of
+// the two neighbours, one-sided (doubled) when only one is valid, 0 when none
+// is.  Valid = inside the global volume and weight != 0.  A slab's owned items
+// read slices z - 1 .. z + 2 only: inside its kSlabHalo stored halo.
+__device__ __forceinline__ f3 tsdf_gradient(const VolView &v, int x, int y, int z, float Fq) {
+  float g[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int q = k == 0 ? x : (k == 1 ? y : z), dim = k == 0 ? v.X : (k == 1 ? v.Y : v.Z);
+    float hi = Fq, lo = Fq;
+    int valid = 0;
+    if (q + 1 < dim) {
+      const size_t j = vox_index(v, x + (k == 0), y + (k == 1), z + (k == 2));
+      if (v.weight[j] != 0) {
+        hi = (float)v.tsdf[j] * kDivShortMax;
+        ++valid;
+      }
+    }
+    if (q >= 1) {
+      const size_t j = vox_index(v, x - (k == 0), y - (k == 1), z - (k == 2));
+      if (v.weight[j] != 0) {
+        lo = (float)v.tsdf[j] * kDivShortMax;
+        ++valid;
+      }
+    }
+    float d = hi - lo;
+    if (valid == 1) d = d * 2.f;
+    g[k] = d / v.vs[k];
+  }
+  return {g[0], g[1], g[2]};
+}
+// The 4 attribute words {nx, ny, nz, b | g<<8 | r<<16 | a<<24} of the vertex on
+// the grid edge from voxel a = (x, y, z) to b = a + e_axis, written as integers
+// (the colour word is never a float).  Called by emitting lanes only: the
+// loads hit the bricks the wave has just read.
+__device__ __forceinline__ void vertex_attr(const VolView &v, const DevPose &aff, int x, int y, int z, int axis,
+                                            uint32_t *dst) {
+  const int xb = x + (axis == 0), yb = y + (axis == 1), zb = z + (axis == 2);
+  const size_t ia = vox_index(v, x, y, z), ib = vox_index(v, xb, yb, zb);
+  const int qa = v.tsdf[ia], qb = v.tsdf[ib];
+  const float Fa = (float)qa * kDivShortMax, Fb = (float)qb * kDivShortMax;
+  const f3 ga = tsdf_gradient(v, x, y, z, Fa), gb = tsdf_gradient(v, xb, yb, zb, Fb);
+  const float wa = fabsf(Fb), wb = fabsf(Fa);  // a's share is b's distance, as for the position
+  const f3 m = {ga.x * wa + gb.x * wb, ga.y * wa + gb.y * wb, ga.z * wa + gb.z * wb};
+  const f3 w = rmul(aff.R, m);
+  const float l = sqrtf(w.x * w.x + w.y * w.y + w.z * w.z);
+  f3 n = {0.f, 0.f, 0.f};
+  if (l != 0.f) n = {w.x / l, w.y / l, w.z / l};
+  const uint32_t ca = v.rgb[ia] & 0xffffffu, cb = v.rgb[ib] & 0xffffffu;
+  uint32_t col = 0u;
+  if (ca != 0u && cb != 0u) {
+    const uint32_t ta = (uint32_t)abs(qa), tb = (uint32_t)abs(qb), den = ta + tb;  // den > 0: a crossing
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      col |= ((((ca >> (8 * j)) & 0xffu) * tb + ((cb >> (8 * j)) & 0xffu) * ta + (den >> 1)) / den) << (8 * j);
+    col |= 0xff000000u;
+  } else if ((ca | cb) != 0u) {
+    col = (ca | cb) | 0xff000000u;
+  }
+  dst[0] = __float_as_uint(n.x);
+  dst[1] = __float_as_uint(n.y);
+  dst[2] = __float_as_uint(n.z);
+  dst[3] = col;
+}
+// words per attributed vertex (kfx_vertex)
+constexpr int kVertexWords = 7;
+__device__ __forceinline__ void st_vertex(uint32_t *dst, f3 p) {
+  dst[0] = __float_as_uint(p.x);
+  dst[1] = __float_as_uint(p.y);
+  dst[2] = __float_as_uint(p.z);
+}
+
+// axes (kAttr): the edge axis of point l in bits 2l, 2l + 1
+template <bool kAttr = false>
 __device__ __forceinline__ int extract_voxel(const VolView &v, const DevPose &aff, int x, int y,
-                                             int z, f3 (&pts)[3]) {
+                                             int z, f3 (&pts)[3], int *axes = nullptr) {
   const size_t i = vox_index(v, x, y, z);
   const int W = v.weight[i];
   const float F = (float)v.tsdf[i] * kDivShortMax;
@@ -2928,6 +3004,7 @@ __device__ __forceinline__ int extract_voxel(const VolView &v, const DevPose &af
       if (axis == 0) p.x = c;
       else if (axis == 1) p.y = c;
       else p.z = c;
+      if constexpr (kAttr) *axes |= axis << (2 * n);
       pts[n++] = add(rmul(aff.R, p), t);
     }
   };
@@ -2954,7 +3031,8 @@ __device__ __forceinline__ bool brick_clear(const VolView &v, int tile, int c0) 
 // One extraction wave's brick (lanes = the tile's 64 columns, slices [z0, z1)):
 // kEmit = false returns the wave's point count; true writes the points at
 // base + (canonical rank) (rank < cap only) and returns the count too.
-template <bool kEmit>
+// kAttr (emit only): 7-word attributed points (kfx_vertex) instead of float3.
+template <bool kEmit, bool kAttr = false>
 __device__ __forceinline__ unsigned extract_wave(const VolView &v, const DevPose &aff, int x, int y, int z0,
                                                  int z1, unsigned long long base, float *out,
                                                  unsigned long long cap) {
@@ -2963,7 +3041,8 @@ __device__ __forceinline__ unsigned extract_wave(const VolView &v, const DevPose
   const unsigned long long below = (1ull << lane) - 1ull;
   for (int z = z0; z < z1; ++z) {
     f3 pts[3];
-    const int n = extract_voxel(v, aff, x, y, z, pts);
+    int axes = 0;
+    const int n = extract_voxel<kEmit && kAttr>(v, aff, x, y, z, pts, &axes);
     const unsigned long long b1 = __ballot(n >= 1), b2 = __ballot(n >= 2), b3 = __ballot(n >= 3);
     if (kEmit) {
       const unsigned long long r = base + (unsigned long long)(__popcll(b1 & below) +
@@ -2971,7 +3050,15 @@ __device__ __forceinline__ unsigned extract_wave(const VolView &v, const DevPose
                                                                __popcll(b3 & below));
 #pragma unroll
       for (int l = 0; l < 3; ++l)  // (unrolled: pts stays in registers)
-        if (l < n && r + l < cap) st3(out, (size_t)(r + l), pts[l]);
+        if (l < n && r + l < cap) {
+          if constexpr (kAttr) {
+            uint32_t *dst = reinterpret_cast<uint32_t *>(out) + (size_t)(r + l) * kVertexWords;
+            st_vertex(dst, pts[l]);
+            vertex_attr(v, aff, x, y, z, (axes >> (2 * l)) & 3, dst + 3);
+          } else {
+            st3(out, (size_t)(r + l), pts[l]);
+          }
+        }
     }
     const unsigned wt = (unsigned)(__popcll(b1) + __popcll(b2) + __popcll(b3));
     base += wt;
@@ -2989,8 +3076,10 @@ __device__ __forceinline__ unsigned extract_wave(const VolView &v, const DevPose
 // centres as the point extraction does (FullScan6, tsdf_volume.cu:341-360),
 // then the volume pose.  Triangles come out in the canonical order of the
 // point cloud (8-slice chunk, tile, z, lane, triangle), 9 floats each.
+// kAttr: also writes the 7-word attributed vertex (kfx_vertex) to dst.
+template <bool kAttr = false>
 __device__ __forceinline__ f3 mc_vertex(const VolView &v, const DevPose &aff, int x, int y, int z, int e,
-                                        const float (&F)[8]) {
+                                        const float (&F)[8], uint32_t *dst = nullptr) {
   const int a = e >> 2, k = e & 3;
   // lower corner of edge e: the k-th corner (ascending) with bit a clear
   int c = 0, m = 0;
@@ -3010,12 +3099,18 @@ __device__ __forceinline__ f3 mc_vertex(const VolView &v, const DevPose &aff, in
   if (a == 0) V.x = cc;
   else if (a == 1) V.y = cc;
   else V.z = cc;
-  return add(rmul(aff.R, V), {aff.t[0], aff.t[1], aff.t[2]});
+  const f3 p = add(rmul(aff.R, V), {aff.t[0], aff.t[1], aff.t[2]});
+  if constexpr (kAttr) {
+    st_vertex(dst, p);
+    vertex_attr(v, aff, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1), a, dst + 3);
+  }
+  return p;
 }
 
 // One marching-cubes wave's brick (as extract_wave): triangles in the
 // canonical order, 9 floats each.
-template <bool kEmit>
+// kAttr (emit only): 21 words per triangle (3 kfx_vertex).
+template <bool kEmit, bool kAttr = false>
 __device__ __forceinline__ unsigned mesh_wave(const VolView &v, const DevPose &aff, const uint8_t *__restrict__ tab,
                                               int x, int y, int z0, int z1, unsigned long long base, float *out,
                                               unsigned long long cap) {
@@ -3047,8 +3142,13 @@ __device__ __forceinline__ unsigned mesh_wave(const VolView &v, const DevPose &a
       for (int t = 0; t < nt; ++t) {
         if (r0 + t >= cap) break;
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-          st3(out, (size_t)(3 * (r0 + t) + k), mc_vertex(v, aff, x, y, z, tab[16 * cfg + 1 + 3 * t + k], F));
+        for (int k = 0; k < 3; ++k) {
+          if constexpr (kAttr)
+            (void)mc_vertex<true>(v, aff, x, y, z, tab[16 * cfg + 1 + 3 * t + k], F,
+                                  reinterpret_cast<uint32_t *>(out) + (size_t)(3 * (r0 + t) + k) * kVertexWords);
+          else
+            st3(out, (size_t)(3 * (r0 + t) + k), mc_vertex(v, aff, x, y, z, tab[16 * cfg + 1 + 3 * t + k], F));
+        }
       }
     }
     const unsigned wt = (unsigned)__shfl(incl, 63);
@@ -3082,7 +3182,9 @@ enum XMode { kXCount = 0, kXEmit = 1, kXPool = 2 };
 // pool emit); small volumes keep enough waves with a small K.
 // kXCount: counts[unit]; kXEmit: items at offsets[unit] (first cap only);
 // kXPool: counts[unit] and the items into the pool (above).
-template <int kMode, bool kMesh>
+// kAttr (kXEmit / kXPool): attributed items, 7 words per point, 21 per
+// triangle, in place of 3 / 9 floats (the count pass needs no attributes).
+template <int kMode, bool kMesh, bool kAttr = false>
 __global__ __launch_bounds__(256) void k_xsweep(VolView v, DevPose aff, int zlo, int zhi,
                                                 const uint8_t *__restrict__ tab, unsigned *counts,
                                                 const unsigned long long *offsets, float *out,
@@ -3113,9 +3215,9 @@ __global__ __launch_bounds__(256) void k_xsweep(VolView v, DevPose aff, int zlo,
     const int y = (tile / v.tiles_x) * 8 + (lane >> 3);
     if (kMode == kXEmit) {
       if (kMesh)
-        (void)mesh_wave<true>(v, aff, tab, x, y, z0, z1, offsets[unit], out, cap);
+        (void)mesh_wave<true, kAttr>(v, aff, tab, x, y, z0, z1, offsets[unit], out, cap);
       else
-        (void)extract_wave<true>(v, aff, x, y, z0, z1, offsets[unit], out, cap);
+        (void)extract_wave<true, kAttr>(v, aff, x, y, z0, z1, offsets[unit], out, cap);
       continue;
     }
     const unsigned n = kMesh ? mesh_wave<false>(v, aff, tab, x, y, z0, z1, 0ull, out, 0ull)
@@ -3137,18 +3239,19 @@ __global__ __launch_bounds__(256) void k_xsweep(VolView v, DevPose aff, int zlo,
     // the items again from the brick just read (cache hits; staging them in
     // LDS during the count measured slower: occupancy)
     if (kMesh)
-      (void)mesh_wave<true>(v, aff, tab, x, y, z0, z1, base, out, cap);
+      (void)mesh_wave<true, kAttr>(v, aff, tab, x, y, z0, z1, base, out, cap);
     else
-      (void)extract_wave<true>(v, aff, x, y, z0, z1, base, out, cap);
+      (void)extract_wave<true, kAttr>(v, aff, x, y, z0, z1, base, out, cap);
   }
 }
 // Pass C: listed wave i's items from the pool to offsets[wave] (first cap
-// items of the canonical order only); per = floats per item.
+// items of the canonical order only); per = 32-bit words per item, copied as
+// integers (an attributed item's colour word is no float).
 __global__ __launch_bounds__(256) void k_extract_copy(const unsigned *__restrict__ list, unsigned nlist,
                                                       const unsigned *__restrict__ counts,
                                                       const unsigned long long *__restrict__ pool_at,
                                                       const unsigned long long *__restrict__ offsets,
-                                                      const float *__restrict__ pool, float *out,
+                                                      const uint32_t *__restrict__ pool, uint32_t *out,
                                                       unsigned long long cap, int per) {
   const unsigned i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= nlist) return;
@@ -3157,8 +3260,8 @@ __global__ __launch_bounds__(256) void k_extract_copy(const unsigned *__restrict
   const unsigned long long o = offsets[w];
   if (o >= cap) return;
   const unsigned long long n = min((unsigned long long)counts[w], cap - o);
-  const float *src = pool + pool_at[w] * per;
-  float *dst = out + o * per;
+  const uint32_t *src = pool + pool_at[w] * per;
+  uint32_t *dst = out + o * per;
   for (unsigned long long k = lane; k < n * per; k += 64) dst[k] = src[k];
 }
 
@@ -3920,7 +4023,7 @@ static int extract_chunks(int zlo, int zhi) {
 size_t extract_waves(const VolView &v, int zlo, int zhi) {
   return (size_t)v.tiles_x * v.tiles_y * (size_t)extract_chunks(zlo, zhi);
 }
-template <int kMode>
+template <int kMode, bool kAttr = false>
 static void launch_xsweep(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
                           unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap,
                           unsigned long long *ctr, unsigned long long *pool_at, unsigned *list, unsigned *overflow) {
@@ -3933,23 +4036,30 @@ static void launch_xsweep(hipStream_t s, const VolView &v, DevPose vpose, int zl
   while (K < 64 && units / (size_t)(2 * K) >= (size_t)KFX_XSWEEP_WAVES) K *= 2;
   dim3 grd((tiles + 4 * K - 1) / (4 * K), nc);  // 4 waves of K units per block
   if (tab)
-    hipLaunchKernelGGL((k_xsweep<kMode, true>), grd, dim3(256), 0, s, v, vpose, zlo, zhi, tab, counts, offsets, out,
-                       cap, ctr, pool_at, list, overflow, K);
+    hipLaunchKernelGGL((k_xsweep<kMode, true, kAttr>), grd, dim3(256), 0, s, v, vpose, zlo, zhi, tab, counts, offsets,
+                       out, cap, ctr, pool_at, list, overflow, K);
   else
-    hipLaunchKernelGGL((k_xsweep<kMode, false>), grd, dim3(256), 0, s, v, vpose, zlo, zhi, tab, counts, offsets, out,
-                       cap, ctr, pool_at, list, overflow, K);
+    hipLaunchKernelGGL((k_xsweep<kMode, false, kAttr>), grd, dim3(256), 0, s, v, vpose, zlo, zhi, tab, counts, offsets,
+                       out, cap, ctr, pool_at, list, overflow, K);
 }
 void launch_extract(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi,
                     unsigned *counts, const unsigned long long *offsets, float *out,
-                    unsigned long long cap) {
-  if (offsets)
+                    unsigned long long cap, bool attr) {
+  if (offsets && attr)
+    launch_xsweep<kXEmit, true>(s, v, vpose, zlo, zhi, nullptr, counts, offsets, out, cap, nullptr, nullptr, nullptr,
+                                nullptr);
+  else if (offsets)
     launch_xsweep<kXEmit>(s, v, vpose, zlo, zhi, nullptr, counts, offsets, out, cap, nullptr, nullptr, nullptr, nullptr);
   else
     launch_xsweep<kXCount>(s, v, vpose, zlo, zhi, nullptr, counts, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
 }
 void launch_mesh(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
-                 unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap) {
-  if (offsets)
+                 unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap,
+                 bool attr) {
+  if (offsets && attr)
+    launch_xsweep<kXEmit, true>(s, v, vpose, zlo, zhi, tab, counts, offsets, out, cap, nullptr, nullptr, nullptr,
+                                nullptr);
+  else if (offsets)
     launch_xsweep<kXEmit>(s, v, vpose, zlo, zhi, tab, counts, offsets, out, cap, nullptr, nullptr, nullptr, nullptr);
   else
     launch_xsweep<kXCount>(s, v, vpose, zlo, zhi, tab, counts, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
@@ -3957,15 +4067,19 @@ void launch_mesh(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zh
 size_t scan_blocks(size_t n) { return (n + 4095) / 4096; }
 void launch_extract_pool(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
                          unsigned *counts, unsigned long long *ctr, unsigned long long *pool_at, unsigned *list,
-                         float *pool, unsigned long long pool_cap, unsigned *overflow) {
-  launch_xsweep<kXPool>(s, v, vpose, zlo, zhi, tab, counts, nullptr, pool, pool_cap, ctr, pool_at, list, overflow);
+                         float *pool, unsigned long long pool_cap, unsigned *overflow, bool attr) {
+  if (attr)
+    launch_xsweep<kXPool, true>(s, v, vpose, zlo, zhi, tab, counts, nullptr, pool, pool_cap, ctr, pool_at, list,
+                                overflow);
+  else
+    launch_xsweep<kXPool>(s, v, vpose, zlo, zhi, tab, counts, nullptr, pool, pool_cap, ctr, pool_at, list, overflow);
 }
 void launch_extract_copy(hipStream_t s, const unsigned *list, unsigned nlist, const unsigned *counts,
                          const unsigned long long *pool_at, const unsigned long long *offsets, const float *pool,
                          float *out, unsigned long long cap, int per) {
   if (nlist == 0) return;
   hipLaunchKernelGGL(k_extract_copy, dim3((nlist + 3) / 4), dim3(256), 0, s, list, nlist, counts, pool_at, offsets,
-                     pool, out, cap, per);
+                     reinterpret_cast<const uint32_t *>(pool), reinterpret_cast<uint32_t *>(out), cap, per);
 }
 void launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offsets,
                  unsigned long long *bsum, size_t n, unsigned long long *total) {

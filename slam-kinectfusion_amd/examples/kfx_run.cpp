@@ -1,8 +1,9 @@
 // kfx_run — the reference's main.cpp loop (main.cpp:63-98) on a dataset
 // directory, over the C-ABI only (no OpenCV, no viz): depth_sensor::open /
 // getFrame → kinectfusion::pipeline per frame → poses.txt (and optionally the
-// point cloud PLY, main.cpp:43-44).
-//   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply]
+// point cloud PLY, main.cpp:43-44; the coloured, oriented cloud and mesh are
+// extensions: kfx_save_pointcloud_attr / kfx_save_mesh_attr).
+//   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply]
 #include <chrono>
 #include <cstdio>
 #include <vector>
@@ -11,7 +12,8 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s <dataset dir> [poses.txt] [cloud.ply]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply]\n",
+                 argv[0]);
     return 2;
   }
   const char *poses = argc > 2 ? argv[2] : "poses.txt";
@@ -59,7 +61,9 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "error: %s\n", kfx_last_error());
     return 1;
   }
-  if (argc > 3 && kfx_save_pointcloud(ctx, argv[3], 0) != KFX_OK) {
+  if ((argc > 3 && kfx_save_pointcloud(ctx, argv[3], 0) != KFX_OK) ||
+      (argc > 4 && kfx_save_pointcloud_attr(ctx, argv[4], 0) != KFX_OK) ||
+      (argc > 5 && kfx_save_mesh_attr(ctx, argv[5], 0) != KFX_OK)) {
     std::fprintf(stderr, "error: %s\n", kfx_last_error());
     return 1;
   }

@@ -19,7 +19,8 @@ from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, Intr
                   default_params, fptr, i16ptr, i64ptr, u8ptr, u16ptr)
 
 __all__ = ["KinectFusion", "KfxError", "Dataset", "png_info", "png_read_bgr8", "png_read_depth", "parse_intr",
-           "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
+           "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "write_ply_attr", "write_ply_mesh_attr",
+           "VERTEX_DTYPE", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
            "default_params", "KFX_FRAME_CUR", "KFX_FRAME_PREV", "KFX_OK", "KFX_TRACKING_LOST", "EXPORTS"]
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,6 +37,8 @@ EXPORTS = [
     "kfx_integrate_counts", "kfx_integrate_stats", "kfx_raycast_stats", "kfx_download_columns", "kfx_pipeline_async", "kfx_pipeline_async_u16", "kfx_register_host_buffer", "kfx_unregister_host_buffer", "kfx_slab_mask_payload", "kfx_slab_expand", "kfx_set_icp_allreduce", "kfx_create_slab", "kfx_create_slab_cuts", "kfx_slice_work", "kfx_slice_work_parts", "kfx_slice_work_at", "kfx_get_graph_mode", "kfx_get_graph_note", "kfx_slab_balance", "kfx_slab_info", "kfx_comm_get_unique_id", "kfx_comm_init",
     "kfx_pipeline_group", "kfx_slab_frame_local", "kfx_slab_frame_finish", "kfx_render", "kfx_volume_checksum", "kfx_extract_points", "kfx_write_ply", "kfx_save_pointcloud",
     "kfx_extract_mesh", "kfx_write_ply_mesh", "kfx_get_extract_ms", "kfx_set_extract_passes", "kfx_get_extract_passes", "kfx_set_slab_bound",
+    "kfx_extract_points_attr", "kfx_extract_mesh_attr", "kfx_write_ply_attr", "kfx_write_ply_mesh_attr",
+    "kfx_save_pointcloud_attr", "kfx_save_mesh_attr",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
 ]
@@ -137,6 +140,12 @@ def lib():
         "kfx_set_slab_bound": ([vp, i], i),
         "kfx_get_extract_passes": ([vp, P(i)], i),
         "kfx_write_ply_mesh": ([C.c_char_p, P(f), C.c_int64], i),
+        "kfx_extract_points_attr": ([vp, vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_extract_mesh_attr": ([vp, vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_write_ply_attr": ([C.c_char_p, vp, C.c_int64], i),
+        "kfx_write_ply_mesh_attr": ([C.c_char_p, vp, C.c_int64], i),
+        "kfx_save_pointcloud_attr": ([vp, C.c_char_p, C.c_int64], i),
+        "kfx_save_mesh_attr": ([vp, C.c_char_p, C.c_int64], i),
         "kfx_dataset_open": ([C.c_char_p, P(vp)], i),
         "kfx_dataset_info": ([vp, P(Intrinsics), P(i), P(i)], i),
         "kfx_dataset_read": ([vp, i, P(C.c_uint8), P(f)], i),
@@ -191,6 +200,23 @@ def write_ply(path: str, xyz: np.ndarray):
     """kinectfusion::savePointcloud's ASCII PLY for an (N, 3) float32 array."""
     xyz = np.ascontiguousarray(xyz, np.float32)
     _check(lib().kfx_write_ply(path.encode(), fptr(xyz), xyz.shape[0]), "kfx_write_ply")
+
+
+# kfx_vertex (include/kfx.h): position, unit normal, colour in the ABI's BGR order + a (255: coloured)
+VERTEX_DTYPE = [("xyz", "<f4", 3), ("normal", "<f4", 3), ("bgra", "u1", 4)]
+
+
+def write_ply_attr(path: str, verts: np.ndarray):
+    """ASCII PLY (x y z nx ny nz red green blue) of an (N,) VERTEX_DTYPE array."""
+    v = np.ascontiguousarray(verts, np.dtype(VERTEX_DTYPE)).ravel()
+    _check(lib().kfx_write_ply_attr(path.encode(), v.ctypes.data_as(C.c_void_p), v.shape[0]), "kfx_write_ply_attr")
+
+
+def write_ply_mesh_attr(path: str, tris: np.ndarray):
+    """ASCII PLY of an (N, 3) VERTEX_DTYPE triangle soup: 3N attributed vertices, N faces."""
+    t = np.ascontiguousarray(tris, np.dtype(VERTEX_DTYPE)).reshape(-1, 3)
+    _check(lib().kfx_write_ply_mesh_attr(path.encode(), t.ctypes.data_as(C.c_void_p), t.shape[0]),
+           "kfx_write_ply_mesh_attr")
 
 
 def png_info(path: str) -> tuple:
@@ -540,11 +566,29 @@ class KinectFusion:
                "kfx_extract_points")
         return _trim(out, min(n.value, max(cap, 0)))
 
-    def extract_count(self, mesh: bool = False) -> int:
-        """Points (or triangles) the volume holds, without extracting them (count pass only)."""
+    def extract_points_attr(self, cap: int = 10_000_000) -> np.ndarray:
+        """extract_points with a unit normal and the fused colour per point: (N,) VERTEX_DTYPE,
+        item i = point i of extract_points (same order, total and cap prefix)."""
         n = C.c_int64()
-        fn = lib().kfx_extract_mesh if mesh else lib().kfx_extract_points
-        _check(fn(self._h, None, 0, C.byref(n)), "kfx_extract_mesh" if mesh else "kfx_extract_points")
+        out = np.empty(max(cap, 0), np.dtype(VERTEX_DTYPE))
+        _check(lib().kfx_extract_points_attr(self._h, out.ctypes.data_as(C.c_void_p) if cap > 0 else None,
+                                             max(cap, 0), C.byref(n)), "kfx_extract_points_attr")
+        return _trim(out, min(n.value, max(cap, 0)))
+
+    def extract_mesh_attr(self, cap: int = 50_000_000) -> np.ndarray:
+        """extract_mesh with a unit normal and the fused colour per vertex: (N, 3) VERTEX_DTYPE."""
+        n = C.c_int64()
+        out = np.empty((max(cap, 0), 3), np.dtype(VERTEX_DTYPE))
+        _check(lib().kfx_extract_mesh_attr(self._h, out.ctypes.data_as(C.c_void_p) if cap > 0 else None,
+                                           max(cap, 0), C.byref(n)), "kfx_extract_mesh_attr")
+        return _trim(out, min(n.value, max(cap, 0)))
+
+    def extract_count(self, mesh: bool = False, attr: bool = False) -> int:
+        """Points (or triangles) the volume holds, without extracting them (count pass only);
+        attr: through the _attr call (the same total)."""
+        n = C.c_int64()
+        name = ("kfx_extract_mesh" if mesh else "kfx_extract_points") + ("_attr" if attr else "")
+        _check(getattr(lib(), name)(self._h, None, 0, C.byref(n)), name)
         return n.value
 
     def set_slab_bound(self, mode: int):
@@ -567,6 +611,12 @@ class KinectFusion:
 
     def save_pointcloud(self, path: str, cap: int = 0):
         _check(lib().kfx_save_pointcloud(self._h, path.encode(), cap), "kfx_save_pointcloud")
+
+    def save_pointcloud_attr(self, path: str, cap: int = 0):
+        _check(lib().kfx_save_pointcloud_attr(self._h, path.encode(), cap), "kfx_save_pointcloud_attr")
+
+    def save_mesh_attr(self, path: str, cap: int = 0):
+        _check(lib().kfx_save_mesh_attr(self._h, path.encode(), cap), "kfx_save_mesh_attr")
 
     # ---- Z-slab sharding -------------------------------------------------
     def slab_info(self):
