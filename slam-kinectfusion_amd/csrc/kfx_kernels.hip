@@ -14,6 +14,7 @@
 
 #include "kfx_internal.h"
 #include "kfx_ffadd.h"
+#include "kfx_raystep.h"
 
 #ifndef KFX_INT_KB
 #define KFX_INT_KB 4  // integrate: voxels per batch (loads in flight per lane)
@@ -163,9 +164,6 @@ __device__ __forceinline__ float div_rn(float x, float d, float y) {
   const float r = fmaf(-q0, d, x);
   return fmaf(r, y, q0);
 }
-
-// Two FP32 values in a register pair (the raycast's position / ray-length steps).
-typedef float pf2 __attribute__((ext_vector_type(2)));
 
 // Integrate's voxel pairs (ipf2): the div_rn / rcp_rn / sqrt_rn sequences on
 // two independent operands, as two scalar operations per pair (2 cycles each per
@@ -1980,23 +1978,54 @@ __device__ __forceinline__ float interp(const VolView &v, f3 cf) {
 // interp for volumes whose local voxel count fits 32-bit offsets (k_raycast's
 // kIdx32): the same corners, weights and sum order, but one tile-column index
 // for (gx, gy, gz) and the other seven corners as offsets from it (z + 1 is
-// always the next 64-voxel slice of the same column; x + 1 / y + 1 cross into
-// the next tile only at x & 7 == 7 / y & 7 == 7), read by buffer loads.
-__device__ __forceinline__ float interp32(const VolView &v, __amdgpu_buffer_rsrc_t t, f3 cf) {
+// always the next 64-voxel slice of the same column: the load's +128 B
+// immediate; x + 1 / y + 1 cross into the next tile only at x & 7 == 7 /
+// y & 7 == 7), read by buffer loads.  In three steps, so that the loads of
+// several interpolations share one round trip: the index math (tri32_at), the
+// 8 corner loads (tri32_load) and the weighted sum (tri32_sum).
+struct Tri32 {
+  unsigned o00, o01, o10, o11;  // byte offsets of the (x, y), (x, y+1), (x+1, y), (x+1, y+1) columns at gz
+};
+__device__ __forceinline__ bool tri32_ok(const VolView &v, int gx, int gy, int gz) {
+  return !(gx < 0 || gx >= v.X - 1 || gy < 0 || gy >= v.Y - 1 || gz < 0 || gz >= v.Z - 1) &&
+         !((unsigned)(gz - v.zb) >= (unsigned)(v.zn - 1));
+}
+__device__ __forceinline__ Tri32 tri32_at(const VolView &v, f3 cf) {
   const int gx = f2i_rd(cf.x), gy = f2i_rd(cf.y), gz = f2i_rd(cf.z);
-  if (gx < 0 || gx >= v.X - 1 || gy < 0 || gy >= v.Y - 1 || gz < 0 || gz >= v.Z - 1) return NAN;
-  if ((unsigned)(gz - v.zb) >= (unsigned)(v.zn - 1)) return NAN;
-  const float a = cf.x - (float)gx, b = cf.y - (float)gy, c = cf.z - (float)gz;
+  const bool ok = tri32_ok(v, gx, gy, gz);
   const unsigned col = (unsigned)v.zn << 6;  // voxels per tile column
   const unsigned tile = __umul24((unsigned)gy >> 3, (unsigned)v.tiles_x) + ((unsigned)gx >> 3);
   const unsigned i0 = ((tile * (unsigned)v.zn + (unsigned)(gz - v.zb)) << 6) | (((unsigned)gy & 7u) << 3 | ((unsigned)gx & 7u));
   const unsigned dx = (gx & 7) == 7 ? col - 7u : 1u;
   const unsigned dy = (gy & 7) == 7 ? __umul24((unsigned)v.tiles_x, col) - 56u : 8u;
-  auto ld = [&](unsigned i) {
-    return (float)(int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, i << 1, 0, 0) * kDivShortMax;
-  };
-  const float t000 = ld(i0), t001 = ld(i0 + 64u), t010 = ld(i0 + dy), t011 = ld(i0 + dy + 64u);
-  const float t100 = ld(i0 + dx), t101 = ld(i0 + dx + 64u), t110 = ld(i0 + dx + dy), t111 = ld(i0 + dx + dy + 64u);
+  // (an invalid interpolation reads voxels 0 and 64 and returns NaN)
+  Tri32 q;
+  q.o00 = ok ? i0 << 1 : 0u;
+  q.o01 = ok ? (i0 + dy) << 1 : 0u;
+  q.o10 = ok ? (i0 + dx) << 1 : 0u;
+  q.o11 = ok ? (i0 + dx + dy) << 1 : 0u;
+  return q;
+}
+__device__ __forceinline__ void tri32_load(__amdgpu_buffer_rsrc_t t, const Tri32 &q, int16_t *r) {
+  r[0] = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, q.o00, 0, 0);
+  r[1] = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, q.o00 + 128u, 0, 0);
+  r[2] = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, q.o01, 0, 0);
+  r[3] = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, q.o01 + 128u, 0, 0);
+  r[4] = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, q.o10, 0, 0);
+  r[5] = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, q.o10 + 128u, 0, 0);
+  r[6] = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, q.o11, 0, 0);
+  r[7] = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(t, q.o11 + 128u, 0, 0);
+}
+// (the weights are taken from cf again after the loads: three registers
+// instead of a, b, c carried across the round trip)
+__device__ __forceinline__ float tri32_sum(const VolView &v, f3 cf, const int16_t *r) {
+  const int gx = f2i_rd(cf.x), gy = f2i_rd(cf.y), gz = f2i_rd(cf.z);
+  if (!tri32_ok(v, gx, gy, gz)) return NAN;
+  const float a = cf.x - (float)gx, b = cf.y - (float)gy, c = cf.z - (float)gz;
+  const float t000 = (float)r[0] * kDivShortMax, t001 = (float)r[1] * kDivShortMax;
+  const float t010 = (float)r[2] * kDivShortMax, t011 = (float)r[3] * kDivShortMax;
+  const float t100 = (float)r[4] * kDivShortMax, t101 = (float)r[5] * kDivShortMax;
+  const float t110 = (float)r[6] * kDivShortMax, t111 = (float)r[7] * kDivShortMax;
   float s = 0.f;
   s += t000 * (1 - a) * (1 - b) * (1 - c);
   s += t001 * (1 - a) * (1 - b) * c;
@@ -2009,15 +2038,39 @@ __device__ __forceinline__ float interp32(const VolView &v, __amdgpu_buffer_rsrc
   return s;
 }
 
-// kIdx32 volumes: each of the 6 trilinear interpolations is one round trip of
-// 8 corner loads (interp32); issuing the loads of two or six interpolations
-// before waiting spills registers at the raycast's occupancy budget
-// (DESIGN.md §4).
+// The 6 trilinear interpolations of a normal.  kIdx32 volumes take them in
+// two round trips of three: index math, then 24 corner loads back to back,
+// then the three weighted sums in the reference's order (the registers for
+// the second trip's loads are the first trip's: DESIGN.md §14).  64-bit
+// indices: one round trip of 8 loads per interpolation (interp).
 template <bool kIdx32 = false>
 __device__ f3 compute_normal(const VolView &v, const RayConsts &rc, f3 p) {
-  const __amdgpu_buffer_rsrc_t t = make_rsrc(v.tsdf, kIdx32 ? (unsigned)(2 * v.local_voxels()) : 0u);
-  auto ip = [&](f3 q) { return kIdx32 ? interp32(v, t, mulc(q, rc.vs_inv)) : interp(v, mulc(q, rc.vs_inv)); };
   f3 n;
+  if (kIdx32) {
+    const __amdgpu_buffer_rsrc_t t = make_rsrc(v.tsdf, (unsigned)(2 * v.local_voxels()));
+    int16_t r[24];
+    float f[3];
+    {
+      // (tri32_at and tri32_sum must see the same c0..c2: the sum takes the
+      // cell and weights from them again, bit for bit what the loads used)
+      const f3 c0 = mulc({p.x + rc.gd.x, p.y, p.z}, rc.vs_inv), c1 = mulc({p.x - rc.gd.x, p.y, p.z}, rc.vs_inv),
+               c2 = mulc({p.x, p.y + rc.gd.y, p.z}, rc.vs_inv);
+      tri32_load(t, tri32_at(v, c0), r), tri32_load(t, tri32_at(v, c1), r + 8), tri32_load(t, tri32_at(v, c2), r + 16);
+      f[0] = tri32_sum(v, c0, r), f[1] = tri32_sum(v, c1, r + 8), f[2] = tri32_sum(v, c2, r + 16);
+    }
+    n.x = (f[0] - f[1]) / rc.gd.x;
+    const float fy1 = f[2];
+    {
+      const f3 c0 = mulc({p.x, p.y - rc.gd.y, p.z}, rc.vs_inv), c1 = mulc({p.x, p.y, p.z + rc.gd.z}, rc.vs_inv),
+               c2 = mulc({p.x, p.y, p.z - rc.gd.z}, rc.vs_inv);
+      tri32_load(t, tri32_at(v, c0), r), tri32_load(t, tri32_at(v, c1), r + 8), tri32_load(t, tri32_at(v, c2), r + 16);
+      f[0] = tri32_sum(v, c0, r), f[1] = tri32_sum(v, c1, r + 8), f[2] = tri32_sum(v, c2, r + 16);
+    }
+    n.y = (fy1 - f[0]) / rc.gd.y;
+    n.z = (f[1] - f[2]) / rc.gd.z;
+    return normalized(n);
+  }
+  auto ip = [&](f3 q) { return interp(v, mulc(q, rc.vs_inv)); };
   const float fx1 = ip({p.x + rc.gd.x, p.y, p.z});
   const float fx2 = ip({p.x - rc.gd.x, p.y, p.z});
   n.x = (fx1 - fx2) / rc.gd.x;
@@ -2245,8 +2298,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
     const f3 tmax = {fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z)};
     const float tnear = fmaxf(fmaxf(tmin.x, tmin.y), fmaxf(tmin.x, tmin.z));
     const float tfar = fminf(fminf(tmax.x, tmax.y), fminf(tmax.x, tmax.z));
-    float ray_len = fmaxf(tnear, 0.f);
-    bool live = act && ray_len < tfar;
+    const float ray0 = fmaxf(tnear, 0.f);
+    bool live = act && ray0 < tfar;
     // pass 1: samples up to kb only (the previous frame's model distance
     // along this pixel's ray, + margin; no model point: unbounded)
     uint32_t kb = UINT_MAX;
@@ -2254,13 +2307,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
       const f3 pv = ld3(prev.v[0], o);
       const float dprev = sqrtf(dot(pv, pv));
       if (dprev > 0.f) {
-        const float kf = (dprev * (1.f + ra.bound_rel) + ra.bound_abs - ray_len) / rc.step + 1.f;
+        const float kf = (dprev * (1.f + ra.bound_rel) + ra.bound_abs - ray0) / rc.step + 1.f;
         kb = kf < 1.f ? 1u : (kf < 4.0e9f ? (uint32_t)kf : UINT_MAX);
       }
     }
     const f3 vstep = mulc(dir, rc.vs);
-    ray_len += rc.step;
-    f3 nextp = add(org, scl(dir, ray_len));
+    // The reference's loop `for (; ray_len < tfar; ray_len += step)` starts at
+    // L0 with sample 1; sample k's ray_len is k - 1 adds of step to L0, so the
+    // loop takes samples 1 .. kend - 1 (kfx_raystep.h: its exact trip count,
+    // once per ray).  The march carries only sample indices; a hit candidate's
+    // ray_len is ff_add(L0, step, k - 1).
+    const float L0 = ray0 + rc.step;
+    const uint32_t kend = 1u + (uint32_t)ray_sample_end(L0, rc.step, live ? tfar : L0);
+    f3 nextp = add(org, scl(dir, L0));
     // reference loop state: the carried sample (tsdf_cur for the next step)
     float tprev = live ? voxel2tsdf(v, rc, nextp) : NAN;
     // The march goes kR samples at a time.  Load phase: positions (repeated
@@ -2277,8 +2336,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
     if (kSlab && live) {
       // A slab stores slices [zb, zb + zn): the samples a ray takes before it
       // reaches them read no voxel (NaN: no event, tsdf_volume.cu:184-188), so
-      // the ray jumps over them at once — the exact positions and ray_len of
-      // that many float adds (ff_add), the sample index advanced by as many —
+      // the ray jumps over them at once — the exact positions of that many
+      // float adds (ff_add), the sample index advanced by as many —
       // instead of marching them batch by batch (the middle slabs' rays cross
       // the whole volume before theirs).  The count keeps 1.5 voxels and one
       // sample of margin over the continuous model of the accumulated adds.
@@ -2288,13 +2347,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
       else if (dcz < 0.f) nf = (czv - ((float)(v.zb + v.zn) + 0.5f)) / -dcz;
       if (nf >= 2.f) {
         const int n0 = (int)fminf(nf, 1.0e7f) - 1;
-        const float rl1 = ff_add(ray_len, rc.step, n0 - 1);
         // the reference tests ray_len < tfar before each of the n0 steps
-        if (!(rl1 < tfar)) {
+        // (samples 1 .. n0)
+        if (!((uint32_t)n0 < kend)) {
           live = false;  // the march ends among the skipped samples: no event here
         } else {
           nextp = {ff_add(nextp.x, vstep.x, n0), ff_add(nextp.y, vstep.y, n0), ff_add(nextp.z, vstep.z, n0)};
-          ray_len = rl1 + rc.step;
           kbase += (uint32_t)n0;
           tprev = voxel2tsdf(v, rc, nextp);
           sprev = isnan(tprev) ? 0 : (tprev > 0.f ? 1 : (tprev < 0.f ? -1 : 0));
@@ -2316,10 +2374,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
     // after the candidate sample from the saved state — same samples, same
     // order, same result.
     bool cand = false;
-    f3 cvert = {0.f, 0.f, 0.f}, r_nextp = nextp;
-    float cts = 0.f;  // the candidate's Ts (slab payload)
-    float r_rl = 0.f, r_tprev = 0.f;
-    uint32_t ckey = 0u, r_kbase = 0u;
+    f3 r_nextp = nextp;
+    float cq = 0.f;  // the candidate's Ts = its sample's ray_len - cq
+    float r_tprev = 0.f;
+    uint32_t ckey = 0u;  // the candidate's sample index
     // Empty-space skipping (exact): no event can happen at a sample whose
     // nearest voxel holds no negative tsdf unless the sample before it is
     // negative (every event needs a negative sample: tsdf_volume.cu:242-244).
@@ -2329,11 +2387,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
     // travel; every voxel of the box such a run guarantees (box_limit) is
     // non-negative, and voxels outside the volume (or the stored slab) are
     // NaN.  The samples that stay inside the larger of the two boxes are only
-    // replayed (nextp += vstep, ray_len += step: the reference's exact adds)
-    // without loads; the last one is then loaded as the carried sample.
+    // replayed (nextp += vstep: the reference's exact adds; the sample index
+    // stands for its ray_len) without loads; the last one is then loaded as
+    // the carried sample.
     const f3 dv = mulc(vstep, rc.vs_inv);  // per-sample displacement in voxels
     const f3 idv = {1.f / fabsf(dv.x), 1.f / fabsf(dv.y), 1.f / fabsf(dv.z)};
-    const float rstep = 1.f / rc.step;
     const bool can_skip = !isnan(dv.x + dv.y + dv.z);
     if (kStats || kTrace) st_rays += live ? 1u : 0u;
 #ifdef KFX_RAY_TRACE
@@ -2360,16 +2418,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
             if (kStats) st_blocked += 1;
             break;
           }
-          if (!kSlab && (tfar - ray_len) * rstep + 2.f <= fminf(lim, rc.skip_cap)) {
-            // every sample the loop has left (at most (tfar - ray_len) / step
-            // + 1, 2 of margin over the accumulated rounding) lies in the
-            // clear box: no event follows (tsdf_volume.cu:234), the ray ends
-            // here without a hit and without replaying its last run
+          int n = (int)fminf(lim, rc.skip_cap);
+          const int rem = (int)(kend - kbase - nsk);  // samples the loop has left
+          if (!kSlab && rem <= n) {
+            // every sample the loop has left lies in the clear box: no event
+            // follows (tsdf_volume.cu:234), the ray ends here without a hit
+            // and without replaying its last run
             if (kStats || kTrace) st_lookups += 1;
             live = false;
             break;
           }
-          int n = (int)fminf(lim, rc.skip_cap);
           if (kSlab) {
             // a slab's ray ends 2 slices past its owned range (no owned
             // sample follows, below): replay no further than about there
@@ -2386,36 +2444,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
           t_lk += 1;
           t_mx += (unsigned)n;
 #endif
-          // replay: packed adds {x, y} and {z, ray_len} (the per-element IEEE
-          // adds of the reference); the first nf samples provably stay below
-          // tfar (2 steps of margin over the accumulated rounding)
-          pf2 pxy = {nextp.x, nextp.y}, pzr = {nextp.z, ray_len};
-          const pf2 sxy = {vstep.x, vstep.y}, szr = {vstep.z, rc.step};
-          const int nf = min(n, max(0, (int)((tfar - ray_len) * rstep) - 2));
+          if (kSlab && rem < n) {  // the loop ends inside the skipped samples: no event
+            live = false;
+            break;
+          }
+          // replay: n position adds (the reference's; three scalar adds per
+          // sample, a packed {x, y} add measured the same), all below kend
           int i = 0;
-          for (; i + 8 <= nf; i += 8) {
+          for (; i + 8 <= n; i += 8) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-              pxy = pxy + sxy;
-              pzr = pzr + szr;
-            }
+            for (int u = 0; u < 8; ++u) nextp = add(nextp, vstep);
           }
-          for (; i < nf; ++i) {
-            pxy = pxy + sxy;
-            pzr = pzr + szr;
-          }
-          for (; i < n; ++i) {
-            if (!(pzr.y < tfar)) {  // the loop ends inside the skipped samples: no event
-              live = false;
-              break;
-            }
-            pxy = pxy + sxy;
-            pzr = pzr + szr;
-          }
-          nextp = {pxy.x, pxy.y, pzr.x};
-          ray_len = pzr.y;
+          for (; i < n; ++i) nextp = add(nextp, vstep);
           nsk += (uint32_t)n;
-          if (!live) break;
           if (kSlab) {  // past the owned range (as after a batch): no owned sample follows
             const float zf = nextp.z * rc.vs_inv.z;
             if ((dir.z >= 0.f && zf > (float)(v.own1 + 2)) || (dir.z <= 0.f && zf < (float)(v.own0 - 3))) {
@@ -2441,17 +2482,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
       int16_t raw[kR];
       unsigned pm = 0u, nm = 0u, am = 0u, ownm = 0u;
       if (kStats || kTrace) st_batches += live ? 1u : 0u;
-      float rl = ray_len;
+      // samples of this batch inside the loop's range: j < left
+      const int left = live ? (int)min(kend - kbase, (uint32_t)kR) : 0;
       const f3 p0 = nextp;  // position before the batch's first sample
       // Interior batch: if the first and (estimated) last sample round into the
       // valid (and stored) voxel box with a half-voxel margin and the batch ends
-      // before tfar, every sample of the batch is valid (positions are
+      // before kend, every sample of the batch is valid (positions are
       // monotone per axis along the ray), so the per-sample checks drop out.
       bool interior = !live;
       if (live) {
         const f3 ua = mulc(add(p0, vstep), rc.vs_inv);
         const f3 ub = mulc(add(p0, scl(vstep, (float)kR)), rc.vs_inv);
-        interior = rl + (float)kR * rc.step < tfar && fminf(ua.x, ub.x) >= 1.f &&
+        interior = left == kR && fminf(ua.x, ub.x) >= 1.f &&
                    fmaxf(ua.x, ub.x) <= hx && fminf(ua.y, ub.y) >= 1.f && fmaxf(ua.y, ub.y) <= hy &&
                    fminf(ua.z, ub.z) >= fzlo && fmaxf(ua.z, ub.z) <= fzhi;
       }
@@ -2466,16 +2508,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
           raw[j] = mem.ld(live, (int)fx, (int)fy, (int)fz);  // dead lanes: no access, 0
           pm |= raw[j] > 0 ? (1u << j) : 0u;
           nm |= raw[j] < 0 ? (1u << j) : 0u;
-          rl = rl + rc.step;
         }
         am = (1u << kR) - 1u;
       } else {
 #pragma unroll
       for (int j = 0; j < kR; ++j) {
-        // a is monotone in j (rl only grows), so lanes past tfar or dead
-        // just keep stepping: their samples are masked off
-        const bool a = live && rl < tfar;
-        am |= a ? (1u << j) : 0u;
+        // lanes past kend or dead just keep stepping: their samples are
+        // masked off
+        const bool a = j < left;
         nextp = add(nextp, vstep);
         const float fx = rintf(nextp.x * rc.vs_inv.x);
         const float fy = rintf(nextp.y * rc.vs_inv.y);
@@ -2488,10 +2528,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
         raw[j] = mem.ld(val, (int)fx, (int)fy, (int)fz);
         pm |= (val && raw[j] > 0) ? (1u << j) : 0u;
         nm |= (val && raw[j] < 0) ? (1u << j) : 0u;
-        rl = rl + rc.step;
       }
+      am = (1u << left) - 1u;
       }
-      const int je = __builtin_ctz(~am);  // first sample outside [.., tfar) (kR if none)
+      const int je = __builtin_ctz(~am);  // first sample outside [.., kend) (kR if none)
       // an event at j needs opposite signs at samples j-1, j (tsdf_cur is the
       // previous sample; NaN = sign 0): +/- is a hit candidate, -/+ a stop
       const unsigned pprev = (pm << 1) | (sprev > 0 ? 1u : 0u);
@@ -2513,19 +2553,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
             pend = 0u;
             key = kbase + (uint32_t)j0;
           } else {
-            // sample j0's ray_len: replay the batch's adds (event samples
-            // always lie before je, where every step added rc.step)
-            float tc = tfirst, tn = 0.f, rj = ray_len;
+            float tc = tfirst, tn = 0.f;
 #pragma unroll
             for (int j = 0; j < kR; ++j) {
               const float tj = (float)raw[j] * kDivShortMax;
               if (j + 1 == j0) tc = tj;
               if (j == j0) tn = tj;
-              if (j < j0) rj += rc.step;
             }
-            const float Ts = rj - (v.vs[0] * tc) / (tc - tn);  // A3 (R)
-            cvert = add(org, scl(dir, Ts));
-            cts = Ts;
+            // Ts = ray_len - cq (A3 (R)); the sample's ray_len follows from
+            // ckey in the wave's normal pass
+            cq = (v.vs[0] * tc) / (tc - tn);
             cand = true;
             ckey = kbase + (uint32_t)j0;
             // resume state: sample j0 was processed, the next is j0 + 1
@@ -2534,15 +2571,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
             for (int j = 0; j < kR; ++j)
               if (j <= j0) pj = add(pj, vstep);
             r_nextp = pj;
-            r_rl = rj + rc.step;
-            r_kbase = kbase + (uint32_t)j0 + 1u;
             r_tprev = tn;
             live = false;
             pend = 0u;
           }
         }
       }
-      if (je < kR) live = false;  // left [.., tfar) inside this batch
+      if (je < kR) live = false;  // left [.., kend) inside this batch
       if (kSlab && live) {
         // z is monotonic along the ray: once the samples are more than 2
         // slices past the owned range, no owned sample follows
@@ -2550,7 +2585,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
         if ((dir.z >= 0.f && zf > (float)(v.own1 + 2)) || (dir.z <= 0.f && zf < (float)(v.own0 - 3)))
           live = false;
       }
-      ray_len = rl;
       kbase += kR;
 #ifdef KFX_RAY_TRACE
       {
@@ -2573,9 +2607,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
 #ifdef KFX_RAY_TRACE
     if (__any(cand) && !t_norm) t_norm = wall_clock64();
 #endif
+    bool resume = false;
     if (cand) {  // the wave's normal pass
       cand = false;
-      // (kIdx32 volumes: 32-bit tile-column offsets + buffer loads)
+      // the candidate sample's ray_len: ckey - 1 adds of step to L0 (one exact
+      // fast-forward per pass, kfx_ffadd.h; out of line: inlined, its
+      // temporaries cost the kernel 5 VGPRs)
+      const float Ts = ff_add_call(L0, rc.step, (int)ckey - 1) - cq;
+      const f3 cvert = add(org, scl(dir, Ts));
       const f3 n = compute_normal<kIdx32>(v, rc, cvert);
       if (!isnan(n.x * n.y * n.z)) {
         // Rinv read here (scalar loads of the uniform pose; the transpose of
@@ -2586,16 +2625,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kSlab || !
         nout = rmul(ri, n);
         vout = rmul(ri, sub(cvert, org));
         key = ckey;
-        hts = cts;
+        hts = Ts;
       } else {  // NaN normal: keep marching after the candidate (tsdf_volume.cu:251)
-        live = true;
-        nextp = r_nextp;
-        ray_len = r_rl;
-        kbase = r_kbase;
-        sprev = -1;  // the candidate sample is negative (tsdf_next < 0)
-        tprev = r_tprev;
+        resume = true;
       }
     }
+    // No lane is marching here, and only a resumed lane marches again: every
+    // lane takes the resume state (sample ckey was processed; it is negative,
+    // tsdf_next < 0), so the march state holds no registers during the pass.
+    live = resume;
+    nextp = r_nextp;
+    kbase = ckey + 1u;
+    sprev = -1;
+    tprev = r_tprev;
 #ifdef KFX_RAY_TRACE
     t_ndone = wall_clock64();
 #endif
