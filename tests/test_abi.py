@@ -57,6 +57,60 @@ def test_create_rejects_bad_arguments(kfx_lib):
     assert b"multiples of 8" in kfx_lib.lib().kfx_last_error()
 
 
+def test_create_argument_table(kfx_lib):
+    """The edges of what create_impl accepts (its checks come before the device
+    query, so no GPU is needed): each rejected configuration returns
+    KFX_ERR_ARG, each accepted boundary gets past the checks (KFX_OK with a
+    device, KFX_ERR_NO_DEVICE without one)."""
+    from kfx.abi import Intrinsics
+    KFX_ERR_ARG, KFX_ERR_NO_DEVICE = -1, -5
+    L = kfx_lib.lib()
+
+    def create(w, h, **kw):
+        p = default_params(dims=64, range_m=2.048)
+        for k, v in kw.items():
+            if k == "icp_iter_count":
+                for i, n in enumerate(v):
+                    p.icp_iter_count[i] = n
+            else:
+                setattr(p, k, v)
+        intr = Intrinsics(w, h, 0.8 * w, 0.8 * w, (w - 1) / 2.0, (h - 1) / 2.0)
+        h_ = C.c_void_p()
+        rc = L.kfx_create(C.byref(intr), C.byref(p), 0, C.byref(h_))
+        if rc == 0:
+            L.kfx_destroy(h_)
+        return rc
+
+    rejected = [
+        (328, 248, dict(pyramid_height=4)),                         # 328 = 8 * 41: no multiple of 16
+        (324, 240, dict(pyramid_height=3)),                         # 324 = 4 * 81: no multiple of 8
+        (320, 240, dict(bfilter_kernel_size=0)),
+        (320, 240, dict(bfilter_kernel_size=16)),
+        (16, 12, dict(pyramid_height=2, bfilter_kernel_size=15)),   # level 1 is 8x6: 6 rows <= r = 7
+        (320, 240, dict(dfilter_dist=0.0)),
+        (320, 240, dict(dfilter_dist=30.5)),
+        (320, 240, dict(dfilter_dist=float("nan"))),
+        (320, 240, dict(icp_iter_count=[4, -1, 10, 0])),
+        (320, 240, dict(pyramid_height=0)),
+        (320, 240, dict(pyramid_height=5)),
+    ]
+    for w, h, kw in rejected:
+        assert create(w, h, **kw) == KFX_ERR_ARG, (w, h, kw)
+        assert L.kfx_last_error()
+    accepted = [
+        (24, 16, dict(pyramid_height=1, bfilter_kernel_size=15)),
+        (16, 16, dict(pyramid_height=2, bfilter_kernel_size=15)),   # level 1 is 8x8 > r = 7
+        (32, 32, dict(pyramid_height=3, bfilter_kernel_size=7)),
+        (64, 48, dict(pyramid_height=4, bfilter_kernel_size=11)),   # level 3 is 8x6 > r = 5
+        (40, 24, dict(pyramid_height=3, bfilter_kernel_size=5)),
+        (320, 240, dict(dfilter_dist=30.0)),
+        (320, 240, dict(bfilter_kernel_size=1)),
+        (320, 240, dict(icp_iter_count=[0, 0, 0, 0])),
+    ]
+    for w, h, kw in accepted:
+        assert create(w, h, **kw) in (0, KFX_ERR_NO_DEVICE), (w, h, kw, L.kfx_last_error())
+
+
 def test_product_build_refuses_experiment_macros():
     """make ARCH=gfx950 with -DKFX_* macros is refused for the product library
     (experiments build into lib/var_<name>), and the shipped library source

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from kfx import synth
-from kfx.abi import Intrinsics, Pose, default_params
+from kfx.abi import Intrinsics, Pose, default_params, fptr
 
 f32 = np.float32
 
@@ -103,6 +103,106 @@ def test_bilateral_matches_python_loop(oracle_lib):
                     s1 = f32(s1 + wgt * v)
                     s2 = f32(s2 + wgt)
             assert out[y, x] == f32(s1 / s2)
+
+
+@pytest.mark.parametrize("with_nan", [False, True])
+@pytest.mark.parametrize("ksz", [1, 6, 15])
+def test_bilateral_window_sizes_match_python_loop(ksz, with_nan, oracle_lib):
+    """The loop of test_bilateral_matches_python_loop at the window sizes the
+    GPU parity tests rest on (the smallest, an even one, the largest): taps
+    [y - r, y - r + ksz) with r = ksz // 2, cut at space2 > r * r, on a 10x9
+    image that holds a zero pixel and, in one variant, a NaN pixel (compared by
+    position: it poisons every window that reaches it)."""
+    rng = np.random.default_rng(3)
+    src = (1000 + rng.random((10, 9)) * 40).astype(np.float32)
+    src[4, 5] = 0.0
+    if with_nan:
+        src[7, 2] = np.nan
+    out = oracle_lib.bilateral(src, ksz=ksz, sigma_color=40.0, sigma_spatial=3.0)
+    h, w = src.shape
+    r = ksz // 2
+    assert w > r and h > r  # one reflection reaches every tap
+    sh, ch = f32(-0.5) / f32(3.0 * 3.0), f32(-0.5) / f32(40.0 * 40.0)
+    n_nan = 0
+    with np.errstate(invalid="ignore"):
+        for y in range(h):
+            for x in range(w):
+                c = src[y, x]
+                s1 = s2 = f32(0)
+                for cy in range(y - r, y - r + ksz):
+                    for cx in range(x - r, x - r + ksz):
+                        sp = (x - cx) ** 2 + (y - cy) ** 2
+                        if sp > r * r:
+                            continue
+                        v = src[int(np_reflect101(cy, h)), int(np_reflect101(cx, w))]
+                        d = abs(v - c)
+                        wgt = f32(oracle_lib.expf(float(f32(sp) * sh + (d * d) * ch)))
+                        s1 = f32(s1 + wgt * v)
+                        s2 = f32(s2 + wgt)
+                want = f32(s1 / s2)
+                if np.isnan(want):
+                    n_nan += 1
+                    assert np.isnan(out[y, x]), (y, x)
+                else:
+                    assert out[y, x] == want, (y, x)
+    if with_nan:
+        # the NaN reaches exactly the pixels whose disc holds it (ksz 1: itself)
+        reach = np.zeros((h, w), bool)
+        for y in range(h):
+            for x in range(w):
+                for cy in range(y - r, y - r + ksz):
+                    for cx in range(x - r, x - r + ksz):
+                        if (x - cx) ** 2 + (y - cy) ** 2 <= r * r and \
+                                (int(np_reflect101(cy, h)), int(np_reflect101(cx, w))) == (7, 2):
+                            reach[y, x] = True
+        assert np.array_equal(np.isnan(out), reach) and n_nan == reach.sum() > 0
+    else:
+        assert n_nan == 0 and not np.isnan(out).any()
+        assert out[4, 5] == 0.0  # a zero pixel keeps only its own tap (the others' weights underflow to 0)
+
+
+def _feq(a, b):
+    """Bit equality of float32 arrays, NaNs compared by position."""
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and np.array_equal(na, nb) and \
+        np.array_equal(np.where(na, f32(0), a).view(np.uint32), np.where(nb, f32(0), b).view(np.uint32))
+
+
+@pytest.mark.parametrize("height", [1, 2, 4])
+def test_preprocess_levels_follow_pyramid_height(height, oracle_lib):
+    """kfo_preprocess returns pyramid_height levels, each equal to the pieces
+    called one by one: pyr_down of the raw level below, bilateral, truncation,
+    vertex map, normal map (kinectfusion.cpp:48-76)."""
+    w, h = 64, 48
+    rng = np.random.default_rng(4)
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    d = 1500.0 + 300.0 * np.sin(0.2 * x) + 250.0 * np.cos(0.3 * y) + rng.normal(0.0, 5.0, (h, w))
+    d[rng.random((h, w)) < 0.03] = 0.0
+    d[10:14, 20:30] = 5200.0  # beyond dfilter_dist: cut
+    d = d.astype(np.float32)
+    intr = Intrinsics(w, h, 52.0, 50.0, 30.25, 24.5)
+    p = default_params(dims=64, range_m=2.048)
+    p.pyramid_height = height
+    p.bfilter_kernel_size = 7
+    p.bfilter_spatial_sigma = 3.0
+    p.bfilter_color_sigma = 40.0
+    ds, vs, ns = oracle_lib.preprocess(d, intr, p)
+    assert len(ds) == len(vs) == len(ns) == height
+    raw = d
+    for l in range(height):
+        if l > 0:
+            raw = oracle_lib.pyr_down(raw)
+        li = intr.level(l)
+        assert raw.shape == (li.height, li.width) == (h >> l, w >> l)
+        dm = oracle_lib.bilateral(raw, ksz=7, sigma_color=40.0, sigma_spatial=3.0)
+        oracle_lib.lib().kfo_depth_truncation(fptr(dm), dm.size, p.dfilter_dist)
+        vm = oracle_lib.vertex_map(dm, li)
+        nm = oracle_lib.normal_map(vm)
+        assert _feq(ds[l], dm), l
+        assert _feq(vs[l], vm), l
+        assert _feq(ns[l], nm), l
+        assert (dm > 0).any() and (np.isfinite(nm).all(-1) & (nm != 0).any(-1)).any()
+    assert (ds[0][10:14, 20:30] == 0).all()  # the cut took place
 
 
 def plane_params(dims=64, L=2.0):
