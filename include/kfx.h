@@ -180,6 +180,14 @@ int kfx_debug_force_icp_stall(kfx_ctx *ctx);
  * device_utils.cuh:31, tsdf_volume.cpp:24) at any volume size, so the oracle
  * can pin them at sizes it runs.  Results are identical either way. */
 int kfx_debug_force_index64(kfx_ctx *ctx, int on);
+/* Debug hooks of integrate's settled-brick skip (added under
+ * ABI version 2, nothing else changed).  kfx_debug_count_settled: on != 0
+ * makes every integrate launch count the bricks its waves skip (off by
+ * default).  kfx_debug_get_settled: out[0] = bricks whose settled byte is set
+ * now, out[1] = bricks skipped by the last integrate launch (0 while the
+ * count is off).  Results are identical with the count on or off. */
+int kfx_debug_count_settled(kfx_ctx *ctx, int on);
+int kfx_debug_get_settled(kfx_ctx *ctx, uint64_t out[2]);
 /* Measurement hook (tools/slab_record.py): device time of the sharded ICP's
  * per-rank launches for band `rank` of `world` (kfx_set_icp_allreduce's
  * k_icp_acc over the band's rows of every level + the k_icp_solve, 19

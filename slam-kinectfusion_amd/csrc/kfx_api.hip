@@ -161,6 +161,7 @@ struct kfx_ctx {
   // above alias set `par`, the one the last frame used.
   FrameView curb[2]{};
   float2 *dl0b[2]{};
+  unsigned long long *skipcnt = nullptr;  // VolView::skipcnt's word (kfx_debug_count_settled)
   IcpPlan planb[2]{};
   int par = 0;
   bool overlap = true;
@@ -920,6 +921,10 @@ int do_reset(kfx_ctx *c) {
   HIPCHK(hipMemsetAsync(c->vol.rgb, 0, n * sizeof(uint32_t), c->stream));
   HIPCHK(hipMemsetAsync(c->vol.bocc, 0, c->vol.bocc_bytes(), c->stream));
   HIPCHK(hipMemsetAsync(c->vol.socc, 0, c->vol.socc_bytes(), c->stream));
+  if (c->vol.settled) {
+    HIPCHK(hipMemsetAsync(c->vol.settled, 0, c->vol.settled_bytes(), c->stream));
+    HIPCHK(hipMemsetAsync(c->vol.sgate, 0, 4, c->stream));
+  }
   for (int l = 0; l < c->L; ++l) {
     const size_t np = (size_t)c->g[l].w * c->g[l].h;
     for (FrameView *f : {&c->curb[0], &c->curb[1], &c->prev}) {
@@ -1158,7 +1163,7 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
   // {depth, 1/lambda} per pixel + 16 max-depth shards + the 16x16-pixel max-depth grid
   const size_t grid16 = (size_t)((intr->width + 15) / 16) * ((intr->height + 15) / 16);
   for (float2 *&d : c->dl0b)
-    if ((r = dalloc(c, (void **)&d, np0 * 8 + 64 + grid16 * 4))) return fail(r);
+    if ((r = dalloc(c, (void **)&d, np0 * 8 + 64 + grid16 * 8))) return fail(r);  // (+ the min-depth grid)
   c->vol = make_vol(p, rank, world, cuts);
   // raycast wave durations of the last frame (4 waves per 16x16 block; zeroed: no hint)
   if ((r = dalloc(c, (void **)&c->vol.rdur, grid16 * 4 * sizeof(unsigned)))) return fail(r);
@@ -1175,6 +1180,11 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
   if ((r = dalloc(c, (void **)&c->vol.rgb, n * 4))) return fail(r);
   if ((r = dalloc(c, (void **)&c->vol.bocc, c->vol.bocc_bytes()))) return fail(r);
   if ((r = dalloc(c, (void **)&c->vol.socc, c->vol.socc_bytes()))) return fail(r);
+  // settled-brick bytes (zeroed: none settled) and the debug skip count;
+  // Z-slab contexts keep no bytes and never skip
+  if (world == 1 && (r = dalloc(c, (void **)&c->vol.settled, c->vol.settled_bytes()))) return fail(r);
+  if (world == 1 && (r = dalloc(c, (void **)&c->vol.sgate, 4))) return fail(r);
+  if ((r = dalloc(c, (void **)&c->skipcnt, 8))) return fail(r);
   {  // integrate dispatch order: identity until the first integrate has measured the intervals
     const size_t tiles = (size_t)c->vol.tiles_x * c->vol.tiles_y, items = tiles * integrate_chunks(c->vol);
     if ((r = dalloc(c, (void **)&c->vol.iwork, tiles * 4))) return fail(r);
@@ -1620,6 +1630,36 @@ int kfx_debug_force_index64(kfx_ctx *c, int on) {
     destroy_graphs(c);
   }
   c->vol.force64 = on != 0;
+  return KFX_OK;
+}
+
+int kfx_debug_count_settled(kfx_ctx *c, int on) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((c->vol.skipcnt != nullptr) != (on != 0)) {  // captured frames hold the other argument
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->pstream));
+    destroy_graphs(c);
+    HIPCHK(hipMemset(c->skipcnt, 0, 8));
+  }
+  c->vol.skipcnt = on ? c->skipcnt : nullptr;
+  return KFX_OK;
+}
+
+int kfx_debug_get_settled(kfx_ctx *c, uint64_t out[2]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out) return set_err(KFX_ERR_ARG, "null argument");
+  HIPCHK(hipStreamSynchronize(c->stream));  // the frames enqueued so far (their results stay pending)
+  out[0] = out[1] = 0;
+  if (c->vol.settled) {
+    std::vector<uint8_t> h(c->vol.settled_bytes());
+    HIPCHK(hipMemcpy(h.data(), c->vol.settled, h.size(), hipMemcpyDeviceToHost));
+    for (uint8_t b : h) out[0] += b != 0;
+  }
+  unsigned long long n = 0;
+  HIPCHK(hipMemcpy(&n, c->skipcnt, 8, hipMemcpyDeviceToHost));
+  out[1] = n;
   return KFX_OK;
 }
 

@@ -138,6 +138,18 @@ struct VolView {
   uint32_t *socc;
   int bz0, nbz, bw;
   int sz0, nsz, sw, stx, sty;
+  // Settled free-space bricks (integrate's skip): byte
+  //   settled[tile * bw * 64 + lbz] = 1 <=> every voxel of the brick holds
+  // weight 64 and a tsdf that a ts = 1 update reproduces.  Set by the integrate
+  // wave whose chunk holds the whole brick, cleared by any wave that stores
+  // into the brick and wherever the voxels change outside integrate (reset,
+  // upload).  Null on Z-slab contexts: they never skip.
+  uint8_t *settled;
+  // integrate launches since the last reset (saturating; an upload stores a
+  // large value): below 63 no voxel can hold weight 64, and integrate's waves
+  // leave the settled bookkeeping out.  Allocated with `settled`.
+  unsigned *sgate;
+  unsigned long long *skipcnt;  // kfx_debug_count_settled: bricks skipped by the last integrate (null: not counted)
   // Integrate dispatch order (KFX_INT_LPT): iwork[tile] = the length of the
   // tile's wave-uniform z interval in the last integrate, iperm[b] = the
   // (chunk * tiles + tile) item block b runs (longest estimated first; any
@@ -150,6 +162,7 @@ struct VolView {
   unsigned *rdur;  // raycast: each wave's duration in the last frame (1024-cycle units; issue priority hint)
   __host__ __device__ size_t bocc_bytes() const { return (size_t)tiles_x * tiles_y * bw * 8; }
   __host__ __device__ size_t socc_bytes() const { return (size_t)stx * sty * sw * 4; }
+  __host__ __device__ size_t settled_bytes() const { return (size_t)tiles_x * tiles_y * bw * 64; }
   __host__ __device__ size_t local_voxels() const { return slice * (size_t)zn; }
   // Tile-column layout: the stored slices of one 8x8 column tile are one
   // contiguous run of zn * 64 voxels, z-major inside:

@@ -15,6 +15,7 @@
 #include "kfx_internal.h"
 #include "kfx_ffadd.h"
 #include "kfx_raystep.h"
+#include "kfx_settled.h"
 
 #ifndef KFX_INT_KB
 #define KFX_INT_KB 4  // integrate: voxels per batch (loads in flight per lane)
@@ -257,6 +258,12 @@ __device__ __forceinline__ unsigned *dmax_shards(const float2 *dl0, const LevelG
 // integrate occlusion clip's input (int_tile_clip; the allocation: kfx_api.hip dl0b)
 __device__ __forceinline__ unsigned *dmax_grid(const float2 *dl0, const LevelGeom &g0) {
   return dmax_shards(dl0, g0) + kDmaxShards;
+}
+// ... and behind it the min-depth grid: the least positive level-0 depth of
+// each block (float bits; +inf: none), the settled-brick certificate's input
+// (kfx_settled.h)
+__device__ __forceinline__ unsigned *dmin_grid(const float2 *dl0, const LevelGeom &g0) {
+  return dmax_grid(dl0, g0) + ((g0.w + 15) >> 4) * ((g0.h + 15) >> 4);
 }
 
 // z is the global slice; the view stores slices [zb, zb+zn) (tile-column
@@ -540,14 +547,19 @@ __global__ __launch_bounds__(256) void k_preprocess_maps(BilatArgs a) {
   }
   if (l == 0) {  // block-uniform
     unsigned m = (in && dval > 0.f) ? __float_as_uint(dval) : 0u;
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
-    __shared__ unsigned wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+    unsigned mn = m ? m : 0x7f800000u;  // least positive depth (+inf: none)
+    for (int off = 32; off > 0; off >>= 1) {
+      m = max(m, (unsigned)__shfl_xor((int)m, off));
+      mn = min(mn, (unsigned)__shfl_xor((int)mn, off));
+    }
+    __shared__ unsigned wm[4], wn[4];
+    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m, wn[threadIdx.x >> 6] = mn;
     __syncthreads();
     if (threadIdx.x == 0) {
       const unsigned b = max(max(wm[0], wm[1]), max(wm[2], wm[3]));
       if (b) atomicMax(&dmax_shards(a.dl0, a.t.g[0])[blockIdx.x % kDmaxShards], b);
       dmax_grid(a.dl0, a.t.g[0])[local] = b;  // this 16x16 block's cell (level-0 blocks are row-major)
+      dmin_grid(a.dl0, a.t.g[0])[local] = min(min(wn[0], wn[1]), min(wn[2], wn[3]));
     }
   }
 }
@@ -1569,26 +1581,30 @@ __device__ __forceinline__ void int_tile_clip(const VolView &v, const LevelGeom 
 __device__ __forceinline__ bool int_chunk(const VolView &v, int chunkr, int chunk, int nchunk, int wl, int wh,
                                           int &za, int &zb) {
   const int len = wh - wl + 1;
+  // Inner boundaries move to the nearest multiple of 8 slices inside the
+  // interval, so that a brick lies in one wave's chunk (the settled-brick
+  // skip); a chunk emptied by that (za > zb) has no voxels.
+  auto brick = [&](int b) { return min(max((b + 4) & ~7, wl), wh + 1); };
   if (v.iadapt == 1) {
     // length-capped: chunks of about zn / nchunk slices (a short interval
     // takes fewer; the surplus items, ordered last, exit)
     const int ct = min(nchunk, max(1, (int)(((long long)len * nchunk + v.zn - 1) / v.zn)));
     if (chunk >= ct) return false;
-    za = wl + (int)((long long)len * chunk / ct);
-    zb = wl + (int)((long long)len * (chunk + 1) / ct) - 1;
+    za = chunk == 0 ? wl : brick(wl + (int)((long long)len * chunk / ct));
+    zb = chunk + 1 == ct ? wh : brick(wl + (int)((long long)len * (chunk + 1) / ct)) - 1;
     return true;
   }
   if (chunkr >= 100) {  // equal chunks
-    za = wl + (int)((long long)len * chunk / nchunk);
-    zb = wl + (int)((long long)len * (chunk + 1) / nchunk) - 1;
+    za = chunk == 0 ? wl : brick(wl + (int)((long long)len * chunk / nchunk));
+    zb = chunk + 1 == nchunk ? wh : brick(wl + (int)((long long)len * (chunk + 1) / nchunk)) - 1;
     return true;
   }
   // chunk c gets weight r^c: the chunks dispatched last (highest item
   // index) are the shortest, so the kernel's tail waves are short
   const float r = (float)chunkr * 0.01f;
   const float den = 1.f - __powf(r, (float)nchunk);
-  za = wl + (int)((float)len * ((1.f - __powf(r, (float)chunk)) / den));
-  zb = chunk + 1 == nchunk ? wh : wl + (int)((float)len * ((1.f - __powf(r, (float)(chunk + 1))) / den)) - 1;
+  za = chunk == 0 ? wl : brick(wl + (int)((float)len * ((1.f - __powf(r, (float)chunk)) / den)));
+  zb = chunk + 1 == nchunk ? wh : brick(wl + (int)((float)len * ((1.f - __powf(r, (float)(chunk + 1))) / den))) - 1;
   return true;
 }
 
@@ -1653,6 +1669,10 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
     }
   }
   __syncthreads();
+  if (!kCount && blockIdx.x == 0 && threadIdx.x == 0 && v.settled && s_kind != 2) {  // integrations since the last reset
+    const unsigned n = *v.sgate;
+    if (n < 0x40000000u) *v.sgate = n + 1u;
+  }
 #ifdef KFX_INT_TRACE
   const unsigned long long t_start = wall_clock64();
 #endif
@@ -1675,8 +1695,11 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
       v.weight[i] = 0;
       v.rgb[i] = 0u;
     }
-    if (chunk == 0) {  // the zeroed volume holds no negative tsdf
+    if (chunk == 0) {  // the zeroed volume holds no negative tsdf and no settled brick
       for (int i = lane; i < v.bw; i += 64) v.bocc[(size_t)tile * v.bw + i] = 0ull;
+      if (v.settled)
+        for (int i = lane; i < v.bw * 64; i += 64) v.settled[(size_t)tile * (v.bw * 64) + i] = 0;
+      if (v.settled && tile == 0 && lane == 0) *v.sgate = 0u;
       const int tx = tile % v.tiles_x, ty = tile / v.tiles_x;
       if ((tx & 3) == 0 && (ty & 3) == 0)
         for (int i = lane; i < v.sw; i += 64) v.socc[(size_t)((ty >> 2) * v.stx + (tx >> 2)) * v.sw + i] = 0u;
@@ -1705,14 +1728,47 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   // replay run on the scalar unit)
   za = __builtin_amdgcn_readfirstlane(za);
   zb = __builtin_amdgcn_readfirstlane(zb);
-  z = 1;
+  // The loop's batches start on multiples of kB slices (two of them are one
+  // brick); the up to kB - 1 slices below za pass no test (la >= za).  vc is
+  // the column's position at slice z: z adds from slice 0.
   // (Z-slabs: the fast-forward from a lower count, KFX_FF_MIN_SLAB — every
-  // chunk of a far slab replays its column from z = 1)
-  vc = replay(vc, zs, z, za, v.zb > 0 ? KFX_FF_MIN_SLAB : KFX_FF_MIN);
-  z = max(z, za);
+  // chunk of a far slab replays its column from z = 0)
+  z = za & ~(KFX_INT_KB - 1);
+  vc = replay(vc, zs, 0, z, v.zb > 0 ? KFX_FF_MIN_SLAB : KFX_FF_MIN);
   const int la = max(za, zl), lb = min(zb, zh);  // this lane's voxels of the chunk
   const bool live = lb >= la;
   if (__all(!live)) return;
+  // Settled bricks of this chunk that the frame cannot change (kfx_settled.h):
+  // lane k takes brick gbs + k when the chunk holds all of it; bit k of skipm.
+  // setm: the bytes now set among the bricks the chunk touches (bit k), kept
+  // current by the loop so that it stores a byte only when the byte changes.
+  // (A brick on a chunk boundary is never set inside a launch, so a stale 1
+  // read there only repeats a neighbour's clear.)
+  unsigned long long skipm = 0ull, setm = 0ull;
+  unsigned nskip = 0u;
+  uint8_t *const sett = (!kCount && v.settled) ? v.settled + (size_t)tile * (v.bw * 64) - v.bz0 : nullptr;
+  if (sett) {
+    const int gb = (za >> 3) + lane;
+    const bool inside = gb * 8 >= za && gb * 8 + 7 <= zb;
+    const bool isset = gb * 8 <= zb && sett[gb] != 0;
+    const bool set = inside && isset;
+    setm = __ballot(isset);
+    if (__any(set)) {
+      // the pose again from LDS, into scalar registers (P kept live up to
+      // here in vector registers spills in the clip above)
+      asm volatile("" ::: "memory");
+      DevPose Q;
+      for (int i = 0; i < 9; ++i) Q.R[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_pose.R[i])));
+      for (int i = 0; i < 3; ++i) Q.t[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_pose.t[i])));
+      const bool cert = set && brick_certified(Q.R, Q.t, v.vs[0], v.vs[1], g.fx, g.fy, g.cx, g.cy, g.w, g.h, x & ~7,
+                                               y & ~7, gb * 8, v.trunc, dmin_grid(dl, g), (g.w + 15) >> 4);
+      skipm = __ballot(cert);
+    }
+  }
+  // The bookkeeping runs where it can matter: a byte of the chunk is set, or
+  // the volume has taken the 63 integrations since its last reset without
+  // which no voxel holds weight 64 (VolView::sgate; an upload opens the gate).
+  const bool track = sett && (setm != 0ull || __builtin_amdgcn_readfirstlane(*v.sgate) >= 63u);
 
   const float trunc = v.trunc;
   const float thres_color = trunc / 2;
@@ -1730,7 +1786,9 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   (void)dmap;
   (void)invl;
   constexpr Idx slice = 64;  // index step per z (tile-column layout)
-  Idx iz = (Idx)base + (Idx)(za - v.zb) * slice;  // voxel index of (x, y, z)
+  Idx iz = (Idx)base + (Idx)(z - v.zb) * slice;  // voxel index of (x, y, z) (below the store for z < zb: never used)
+  static_assert(KFX_INT_KB == 4, "two batches per brick");
+  bool sgood = false;  // this lane's voxels of the current brick so far: all updated with ts = 1, nothing changed
   const bool fastw = __all(!live || column_fast(vc, zs, v.Z));  // wave-uniform
   const float fw = (float)g.w, fh = (float)g.h;
   // Batches of kB voxels: positions, projections, the kB {depth, 1/lambda}
@@ -1742,17 +1800,41 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   // sequences; else IEEE division and sqrt) and the wave picks one: the fast
   // loop then carries no code or registers of the other (integrate −2 %,
   // six alternating pairs, against one loop branching on `fast` per batch).
-  auto zloop = [&](auto fast_c) {
+  auto zloop = [&](auto fast_c, auto track_c) {
     constexpr bool fast = decltype(fast_c)::value;
-  for (; z <= zb; z += kB) {
+    constexpr bool track = decltype(track_c)::value;  // the settled bookkeeping (waves that cannot need it carry none)
+  // Runs of slices between certified settled bricks: the batch loop below
+  // carries no skip test; a certified brick is stepped over here (its 8 exact
+  // adds) on the scalar unit.
+  while (z <= zb) {
+    int zrun = zb;  // the run's last slice
+    if constexpr (!kCount) {
+      if (skipm) {
+        const int k = ((z + 7) >> 3) - gbs;  // the first brick that starts at or after z
+        const unsigned long long m = k < 64 ? skipm >> k : 0ull;
+        if (m) {
+          const int zn = (gbs + k + __builtin_ctzll(m)) * 8;  // the next certified brick's first slice
+          if (zn == z) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) vc = add(vc, zs);  // (the loop's own adds: zs stays where the loop keeps it)
+            iz += (Idx)8 * slice;
+            z += 8;
+            ++nskip;
+            continue;
+          }
+          zrun = zn - 1;  // (zn - z is a multiple of kB: the run ends with z == zn)
+        }
+      }
+    }
+  for (; z <= zrun; z += kB) {
     float sdf[kB];
     unsigned pix[kB];
     bool ok[kB];
     f3 p[kB];
 #pragma unroll
     for (int j = 0; j < kB; ++j) {
-      vc = add(vc, zs);
       p[j] = vc;
+      vc = add(vc, zs);
     }
     // projection: ok = in the image in front of the camera (tsdf_volume.cu:56-66)
     if constexpr (fast) {  // the cheap exact sequences, two voxels per packed-FP32 op
@@ -1851,6 +1933,10 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
     // ts = 1 update, sdf >= trunc) needs no test: its update reproduces the
     // stored values, so the changed-value tests below skip its stores.
     int qv[kB];
+    // settled bookkeeping, as wave masks on the scalar unit: lanes with a
+    // voxel that did not pass, and lanes whose update stored something or
+    // ran with sdf < trunc (ts < 1 or the colour band)
+    unsigned long long missm = 0ull, movedm = 0ull;
 #pragma unroll
     for (int j = 0; j < kB; j += 2) {
       const ipf2 tq = div_rn2(ipf2{sdf[j], sdf[j + 1]}, ipf2{trunc, trunc}, ipf2{v.inv_trunc, v.inv_trunc});
@@ -1864,11 +1950,20 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
     }
 #pragma unroll
     for (int j = 0; j < kB; ++j) {
-      if (!ok[j]) continue;
-      const Idx i = vi[j];
+      // the store predicates, for every lane: the ballots below need all lanes
+      // (taken inside the per-voxel branch they would differ between lanes)
       const int pre_w = w0[j];
       const int new_w = min(pre_w + 1, kMaxWeight);
       const int q = qv[j];
+      const bool ct = q != t0[j], cw = new_w != pre_w;
+      if constexpr (track) {
+        // (sdf >= trunc: the quotient is >= 1, so its rounding tq >= 1 and ts = 1,
+        // and the voxel is outside the colour band)
+        missm |= __ballot(!ok[j]);
+        movedm |= __ballot(ok[j] & (ct | cw | !(sdf[j] >= trunc)));
+      }
+      if (!ok[j]) continue;
+      const Idx i = vi[j];
       if (q < 0) {
         const int k = ((z + j) >> 3) - gbs;
         if (k < 62) {
@@ -1880,8 +1975,8 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
       }
       // saturated voxels (w = 64 at a tsdf fixed point) keep their values:
       // skipping those stores changes nothing and saves write bandwidth
-      if (q != t0[j]) mem.st_t(i, (int16_t)q);
-      if (new_w != pre_w) mem.st_w(i, (int16_t)new_w);
+      if (ct) mem.st_t(i, (int16_t)q);
+      if (cw) mem.st_w(i, (int16_t)new_w);
       if (sdf[j] <= thres_color && sdf[j] >= -thres_color) {  // colour band (rare)
         const uint32_t c0 = mem.ld_c(i);
         const uint8_t *px = bgr + 3 * (size_t)(pix[j] >> kPixSh);
@@ -1897,18 +1992,51 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
         if (out != c0) mem.st_c(i, out);
       }
     }
+    // settled bytes (wave-uniform): a store into the brick clears its byte;
+    // the second batch of a brick inside the chunk sets it when all 512
+    // voxels were ts = 1 updates that changed nothing
+    if constexpr (track) {
+      const bool good = !(missm | movedm);
+      sgood = (z & 4) ? (sgood && good) : good;
+      const int k = (z >> 3) - gbs;
+      const unsigned long long kbit = k < 64 ? 1ull << (k & 63) : 0ull;  // (bricks past 64: never set, always cleared)
+      if (movedm) {  // (a superset of the stores: sdf < trunc without one only clears early)
+        if (!kbit || (setm & kbit)) {
+          if (lane == 0) sett[z >> 3] = 0;
+          setm &= ~kbit;
+        }
+      } else if ((z & 4) && sgood && z - 4 >= za && z + 3 <= zb && kbit && !(setm & kbit)) {
+        if (lane == 0) sett[z >> 3] = 1;
+        setm |= kbit;
+      }
+    }
+  }
   }
   };
-  if (fastw) zloop(std::true_type{});
-  else zloop(std::false_type{});
+  if (track) {
+    if (fastw) zloop(std::true_type{}, std::true_type{});
+    else zloop(std::false_type{}, std::true_type{});
+  } else {
+    if (fastw) zloop(std::true_type{}, std::false_type{});
+    else zloop(std::false_type{}, std::false_type{});
+  }
+  if (!kCount && v.skipcnt && nskip && lane == 0) atomicAdd(v.skipcnt, (unsigned long long)nskip);  // debug count
   if (!kCount) {  // raycast skip maps
+    // the exchange addresses are made here from an opaque copy of the lane:
+    // shared with the prologue's shuffles they stay live across the z loop
+    // (six registers the loop has no room for)
+    int el = lane;
+    asm volatile("" : "+v"(el));
+    auto xchg = [&](int val, int off) { return __builtin_amdgcn_ds_bpermute((el ^ off) << 2, val); };
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-      const unsigned lo = __shfl_xor((unsigned)nbm, off), hi = __shfl_xor((unsigned)(nbm >> 32), off);
+      const unsigned lo = (unsigned)xchg((int)(unsigned)nbm, off), hi = (unsigned)xchg((int)(unsigned)(nbm >> 32), off);
       nbm |= ((unsigned long long)hi << 32) | lo;
+      nlo = min(nlo, xchg(nlo, off));
+      nhi = max(nhi, xchg(nhi, off));
     }
     occ_mark_bricks(v, tile, gbs, nbm, lane);
-    occ_mark_wave(v, tile, nlo, nhi, lane);
+    if (nhi >= nlo) occ_mark(v, tile % v.tiles_x, tile / v.tiles_x, nlo, nhi, lane);  // (occ_mark_wave, reduced above)
   }
 #ifdef KFX_INT_TRACE
   if (!kCount && counters && lane == 0) {  // debug: per-wave timeline
@@ -3883,6 +4011,7 @@ void launch_integrate(hipStream_t s, VolView v, LevelGeom g0, const float2 *dl0,
 #define KFX_LAUNCH_INT(C, I)                                                                             \
   hipLaunchKernelGGL((k_integrate<C, I>), grd, dim3(KFX_INT_BLOCK), 0, s, v, g0, dl0, dmap, invl, bgr, st, log, vpose, xpose, \
                      counters)
+  if (!counters && v.skipcnt) (void)hipMemsetAsync(v.skipcnt, 0, 8, s);  // debug: this launch's skipped bricks
   if (counters) KFX_LAUNCH_INT(true, false);
   else if (idx32) KFX_LAUNCH_INT(false, true);
   else KFX_LAUNCH_INT(false, false);
@@ -4288,6 +4417,10 @@ void launch_gather_columns(hipStream_t s, VolView v, const int32_t *cols, int n,
 void launch_occ_rebuild(hipStream_t s, VolView v) {
   (void)hipMemsetAsync(v.bocc, 0, v.bocc_bytes(), s);
   (void)hipMemsetAsync(v.socc, 0, v.socc_bytes(), s);
+  if (v.settled) {  // new contents: no brick is known settled, any may be (the gate opens)
+    (void)hipMemsetAsync(v.settled, 0, v.settled_bytes(), s);
+    (void)hipMemsetAsync(v.sgate, 0x40, 4, s);
+  }
   const size_t waves = (size_t)v.tiles_x * v.tiles_y * v.nbz;
   hipLaunchKernelGGL(k_occ_rebuild, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, v);
 }

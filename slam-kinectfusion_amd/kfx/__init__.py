@@ -39,6 +39,7 @@ EXPORTS = [
     "kfx_extract_mesh", "kfx_write_ply_mesh", "kfx_get_extract_ms", "kfx_set_extract_passes", "kfx_get_extract_passes", "kfx_set_slab_bound",
     "kfx_extract_points_attr", "kfx_extract_mesh_attr", "kfx_write_ply_attr", "kfx_write_ply_mesh_attr",
     "kfx_save_pointcloud_attr", "kfx_save_mesh_attr",
+    "kfx_debug_count_settled", "kfx_debug_get_settled",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
 ]
@@ -86,6 +87,8 @@ def lib():
         "kfx_set_icp_persistent": ([vp, i], i),
         "kfx_debug_force_icp_stall": ([vp], i),
         "kfx_debug_force_index64": ([vp, i], i),
+        "kfx_debug_count_settled": ([vp, i], i),
+        "kfx_debug_get_settled": ([vp, P(C.c_uint64)], i),
         "kfx_debug_icp_band_ms": ([vp, i, i, i, P(C.c_float)], i),
         "kfx_get_icp_trace": ([vp, P(C.c_uint64), i], i),
         "kfx_get_cur_camera_pose": ([vp, P(Pose)], i),
@@ -491,6 +494,16 @@ class KinectFusion:
         """Test hook: integrate / raycast take the 64-bit-index kernels (the
         >= 2^31-voxel path) at any volume size."""
         _check(lib().kfx_debug_force_index64(self._h, int(on)), "kfx_debug_force_index64")
+
+    def debug_count_settled(self, on=True):
+        """Debug hook: integrate counts the settled bricks its waves skip."""
+        _check(lib().kfx_debug_count_settled(self._h, int(on)), "kfx_debug_count_settled")
+
+    def debug_get_settled(self):
+        """(bricks whose settled byte is set, bricks skipped by the last integrate)."""
+        out = (C.c_uint64 * 2)()
+        _check(lib().kfx_debug_get_settled(self._h, out), "kfx_debug_get_settled")
+        return int(out[0]), int(out[1])
 
     def debug_icp_band_ms(self, rank, world, reps=5) -> float:
         """Device ms of the sharded ICP's launches for band rank of world (no
