@@ -188,6 +188,25 @@ int kfx_debug_force_index64(kfx_ctx *ctx, int on);
  * count is off).  Results are identical with the count on or off. */
 int kfx_debug_count_settled(kfx_ctx *ctx, int on);
 int kfx_debug_get_settled(kfx_ctx *ctx, uint64_t out[2]);
+/* Debug hooks of the ICP reduction (added under ABI version 2,
+ * nothing else changed).  kfx_debug_get_icp_sums: the 27 int64 fixed-point
+ * sums (kfx_stage_icp_accumulate's layout) of the last ICP iteration that ran
+ * on this context, whichever kernel ran it; waits for the stream, changes
+ * nothing.  kfx_debug_cap_icp_blocks: cap > 0 plans the persistent ICP as if
+ * at most `cap` blocks were co-resident on the device (a grid below the real
+ * limit is co-resident all the more), cap = 0 restores the device's own
+ * figure; captured graphs are dropped.  cap < 0 changes nothing and only
+ * reports.  Returns 1 if the persistent kernel is
+ * usable under the cap, 0 if not (one launch per iteration then), <0 on
+ * error.  plan (may be NULL) receives the plan in effect: [0] 1 if the
+ * strided kernel form was chosen, [1] blocks of the grid, [2] levels, [3] the
+ * persistent launch in use (0 none, 1 plain, 2 cooperative), then per level l
+ * [4+3l] the contiguous pixel span per block (0: whole pixel groups; in the
+ * strided form groups b, b + blocks, ...), [5+3l] pixel groups (or spans),
+ * [6+3l] pixels per lane.  Results are identical under any cap. */
+#define KFX_ICP_PLAN_WORDS 16
+int kfx_debug_get_icp_sums(kfx_ctx *ctx, int64_t out[27]);
+int kfx_debug_cap_icp_blocks(kfx_ctx *ctx, int cap, int32_t plan[KFX_ICP_PLAN_WORDS]);
 /* Measurement hook (tools/slab_record.py): device time of the sharded ICP's
  * per-rank launches for band `rank` of `world` (kfx_set_icp_allreduce's
  * k_icp_acc over the band's rows of every level + the k_icp_solve, 19

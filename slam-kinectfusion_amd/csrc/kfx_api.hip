@@ -193,6 +193,7 @@ struct kfx_ctx {
   unsigned *icp_ticket = nullptr;
   IcpSync *icp_sync = nullptr;  // persistent ICP barrier + per-iteration shard slots
   IcpPlan icp_plan{};
+  long long icp_exact_pixels = 0;  // pixels one block may sum exactly (icp_exact_pixels of the intrinsics)
   bool icp_persistent = false;  // plan fits and its grid is co-resident
   bool icp_persistent_enabled = true;
   bool icp_coop = false;  // cooperative launch of the persistent ICP (after a watchdog stall, or asked for)
@@ -298,6 +299,19 @@ void set_par(kfx_ctx *c, int p) {
   c->cur = c->curb[p];
   c->dl0 = c->dl0b[p];
   c->icp_plan = c->planb[p];
+}
+
+// The persistent ICP's plans over both buffer sets (the fit may cap nblocks
+// and select the strided kernel).  block_cap > 0: kfx_debug_cap_icp_blocks.
+void plan_icp(kfx_ctx *c, int block_cap) {
+  for (int b = 0; b < 2; ++b) {
+    c->planb[b] = make_icp_plan(c->L, c->g, c->p.icp_iter_count, c->curb[b], c->prev,
+                                c->p.icp_dist_threshold, c->angle_thr);
+    c->planb[b].vpose = to_dev(c->p.volu_pose);
+  }
+  c->icp_persistent = icp_persistent_ok(c->planb[0], c->device, block_cap, c->icp_exact_pixels) &&
+                      icp_persistent_ok(c->planb[1], c->device, block_cap, c->icp_exact_pixels);
+  c->icp_plan = c->planb[c->par];
 }
 
 void destroy_graphs(kfx_ctx *c) {
@@ -1094,10 +1108,21 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
       return set_err(KFX_ERR_ARG, "volume dims must be >= 8 and range > 0");
   if (p.volu_dims[0] % 8 || p.volu_dims[1] % 8)
     return set_err(KFX_ERR_ARG, "volume dims x,y must be multiples of 8 (8x8 slice tiles)");
-  // keeps every in-block ICP fixed-point sum an integer below 2^53 (exact fp64
-  // accumulation in k_icp_acc): |point| stays below ~45 m
   if (!(p.dfilter_dist > 0.f && p.dfilter_dist <= 30.f))
     return set_err(KFX_ERR_ARG, "dfilter_dist must be in (0, 30] m");
+  // the ICP sums' exactness (icp_exact_pixels: one derivation for every kernel form)
+  double icp_B = 0.0;
+  const long long icp_exact = icp_exact_pixels(intr->width, intr->height, intr->fx, intr->fy, intr->cx, intr->cy,
+                                               p.dfilter_dist, &icp_B);
+  if (icp_exact == 0) return set_err(KFX_ERR_ARG, "intrinsics must be finite with fx, fy > 0");
+  if (icp_exact < 1024)
+    return set_err(KFX_ERR_ARG, "field of view x dfilter_dist too large: the farthest vertex (" +
+                                    std::to_string(icp_B) + " m with margin) must stay below 45.25 m for exact ICP sums");
+  if ((double)intr->width * intr->height * icp_B * icp_B >= 2147483648.0)
+    return set_err(KFX_ERR_ARG, "image too large for its farthest vertex: the int64 ICP sums could overflow");
+  // (the residual row entry is at most the distance threshold: it must not exceed the bound's B >= 1 m;
+  // a negative or NaN threshold admits no correspondence and stays legal)
+  if (p.icp_dist_threshold > 1.f) return set_err(KFX_ERR_ARG, "icp_dist_threshold must not exceed 1 m");
   if (p.bfilter_kernel_size < 1 || p.bfilter_kernel_size > 15)
     return set_err(KFX_ERR_ARG, "bfilter_kernel_size must be 1..15");
   for (int l = 0; l < p.pyramid_height; ++l)
@@ -1118,6 +1143,7 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
   c->intr = *intr;
   c->p = p;
   c->L = p.pyramid_height;
+  c->icp_exact_pixels = icp_exact;
   for (int l = 0; l < c->L; ++l) c->g[l] = level_geom(*intr, l);
   c->angle_thr = std::sin(p.icp_angle_threshold * 0.017453293f);  // icp_registration.cpp:5
   int r = KFX_OK;
@@ -1217,12 +1243,7 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
     return fail(r);
   c->icp_ticket = reinterpret_cast<unsigned *>(c->icp_shards + kIcpShards * 27);
   if ((r = dalloc(c, (void **)&c->icp_sync, sizeof(IcpSync)))) return fail(r);
-  for (int b = 0; b < 2; ++b)
-    c->planb[b] = make_icp_plan(c->L, c->g, c->p.icp_iter_count, c->curb[b], c->prev,
-                                c->p.icp_dist_threshold, c->angle_thr);
-  for (int b = 0; b < 2; ++b) c->planb[b].vpose = to_dev(c->p.volu_pose);
-  // (both sets: the fit may cap nblocks and select the strided kernel)
-  c->icp_persistent = icp_persistent_ok(c->planb[0], c->device) && icp_persistent_ok(c->planb[1], c->device);
+  plan_icp(c, 0);
   // The side streams' waits on the raycast start signal run as small spinning
   // kernels, which may be resident while the next frame's persistent ICP
   // starts: keep the signal only when the ICP grid leaves two CUs of headroom
@@ -1663,6 +1684,41 @@ int kfx_debug_get_settled(kfx_ctx *c, uint64_t out[2]) {
   return KFX_OK;
 }
 
+int kfx_debug_get_icp_sums(kfx_ctx *c, int64_t out[27]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out) return set_err(KFX_ERR_ARG, "null argument");
+  DevState s;
+  if ((r = read_state(c, &s))) return r;  // (synchronises the stream)
+  for (int k = 0; k < 27; ++k) out[k] = s.sums[k];
+  return KFX_OK;
+}
+
+int kfx_debug_cap_icp_blocks(kfx_ctx *c, int cap, int32_t plan[KFX_ICP_PLAN_WORDS]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (cap >= 0) {  // (cap < 0: report only, nothing changes)
+    HIPCHK(hipStreamSynchronize(c->pstream));
+    destroy_graphs(c);  // captured frames hold the other plan's launch
+    plan_icp(c, cap);
+  }
+  if (plan) {
+    const IcpPlan &pl = c->icp_plan;
+    for (int k = 0; k < KFX_ICP_PLAN_WORDS; ++k) plan[k] = 0;
+    plan[0] = c->icp_persistent ? pl.stride : 0;
+    plan[1] = pl.nblocks;
+    plan[2] = pl.levels;
+    plan[3] = !c->icp_persistent || !c->icp_persistent_enabled ? 0 : c->icp_coop ? 2 : 1;
+    for (int l = 0; l < pl.levels; ++l) {
+      plan[4 + 3 * l] = c->icp_persistent && pl.stride ? pl.span[l] : 0;
+      plan[5 + 3 * l] = pl.groups[l];
+      plan[6 + 3 * l] = pl.ppl[l];
+    }
+  }
+  return c->icp_persistent ? 1 : 0;
+}
+
 int kfx_set_icp_allreduce(kfx_ctx *c, int enabled) {
   if (!c) return set_err(KFX_ERR_ARG, "null context");
   if (!c->slab) return set_err(KFX_ERR_STATE, "ICP partial all-reduce needs a slab context");
@@ -2013,6 +2069,7 @@ int kfx_stage_icp(kfx_ctx *c, kfx_pose *out) {
   }
   if (out) *out = to_api(s.icp_pose);
   const int failed = s.icp_fail;
+  std::memcpy(s0.sums, s.sums, sizeof(s0.sums));  // the test seam keeps the last iteration's sums (kfx_debug_get_icp_sums)
   HIPCHK(hipMemcpyAsync(c->st, &s0, sizeof(s0), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return failed ? KFX_TRACKING_LOST : KFX_OK;

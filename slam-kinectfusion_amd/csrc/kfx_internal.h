@@ -239,7 +239,12 @@ int icp_blocks(const LevelGeom &g);
 // single launch; shards = 8 x 27 int64 zeroed, ticket zeroed (both self-reset)
 IcpPlan make_icp_plan(int levels, const LevelGeom *g, const int *iters, FrameView cur,
                       FrameView prev, float dist_thr, float angle_thr);
-bool icp_persistent_ok(IcpPlan &pl, int device);  // grid co-resident + slots fit
+// grid co-resident + slots fit; block_cap > 0: as if at most that many blocks
+// were co-resident (kfx_debug_cap_icp_blocks)
+bool icp_persistent_ok(IcpPlan &pl, int device, int block_cap, long long exact_pixels);
+// pixels whose fixed-point ICP terms one block may sum exactly in fp64, from
+// the largest vertex the intrinsics and dfilter_dist produce (*B_out); 0: bad input
+long long icp_exact_pixels(int w, int h, float fx, float fy, float cx, float cy, float dfilter_dist, double *B_out);
 // the persistent ICP grid stays co-resident with `cus_free` CUs' worth of
 // blocks taken by other kernels (icp_persistent_ok's plan)
 bool icp_headroom(const IcpPlan &pl, int device, int cus_free);

@@ -603,9 +603,10 @@ __device__ __forceinline__ double icp_sum_value(long long s) { return (double)s 
 // vertex/normal (n0, v0, validity ok0) are already in registers; gathers the
 // previous frame's maps at the projections and accumulates the 27 products.
 // Every product is rounded to an integer multiple of 2^-32 (rintf(prod *
-// 2^32)); within a block the running sums are integers below 2^49 (|prod| <
-// 2^7, <= 2^10 products per 27-slot), so fp64 adds are exact and equal the
-// oracle's int64 sums; the block total converts to int64 exactly.
+// 2^32)); within a block the running sums are integers below 2^53 for the
+// pixel count icp_exact_pixels derives (checked when the context is created),
+// so fp64 adds are exact and equal the oracle's int64 sums; the block total
+// converts to int64 exactly.
 __device__ __forceinline__ void icp_lane(const LevelGeom &g, const DevPose &P,
                                          const f3 (&n0)[kIcpPix], const f3 (&v0)[kIcpPix],
                                          const bool (&ok0)[kIcpPix], int ppl,
@@ -867,7 +868,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_icp_acc(LevelGeom g, int xe, in
 // (IcpPlan::stride, 1280x720 level 0); block b then takes an equal contiguous
 // range of that level's pixels (IcpPlan::span) in passes of up to kIcpPix per
 // lane, re-reading them every iteration, their products added into the same
-// lane sums (integers below 2^53 for <= 8192 pixels per block, so the fp64
+// lane sums (integers below 2^53 for a span within icp_exact_pixels, so the fp64
 // adds stay exact and the int64 totals are the oracle's); a longer range
 // takes groups b, b + gridDim, ... with one block reduce per group.
 template <bool kStride>
@@ -3745,6 +3746,36 @@ float sqrt_le_bound(float t) {
   return x;
 }
 
+// The ICP sums' exactness contract, in one place.  A pixel's 27 terms are
+// rint(product * 2^32) of two row entries; the entries are v x n (|v x n| <=
+// |v| |n|), the model normal n (unit) and n . (v' - v) (at most the distance
+// threshold, which create keeps at or below 1 m), so |product| <= B^2 with B >= 1 a bound of |v|, the current
+// vertex under the pose being refined.  The preprocess makes vertices depth *
+// ((u - cx) / fx, (v - cy) / fy, 1) with depth <= dfilter_dist, largest at an
+// image corner; the pose adds its translation, for which a margin of 1 m is
+// taken (thirty times the 33 mm a camera moving at 1 m/s covers per frame;
+// the float32 roundings, relative 2^-24 each, vanish in it):
+//   B = dfilter_dist * max over corners |((u - cx) / fx, (v - cy) / fy, 1)| + 1.
+// fp64 additions of integers stay exact while every partial sum is below
+// 2^53, i.e. for n pixels with n * B^2 * 2^32 < 2^53: one block (its lanes'
+// running sums and its reduction tree) may cover floor(2^21 / B^2) pixels.
+// The int64 totals over the level need npix * B^2 * 2^32 < 2^63.
+// Returns that pixel count (0: an intrinsic or the distance is unusable).
+long long icp_exact_pixels(int w, int h, float fx, float fy, float cx, float cy, float dfilter_dist, double *B_out) {
+  if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !(fx > 0.f) ||
+      !(fy > 0.f) || !(dfilter_dist > 0.f) || !std::isfinite(dfilter_dist))
+    return 0;
+  double r2 = 0.0;
+  for (int k = 0; k < 4; ++k) {
+    const double x = ((k & 1 ? w - 1 : 0) - (double)cx) / fx, y = ((k & 2 ? h - 1 : 0) - (double)cy) / fy;
+    r2 = std::max(r2, x * x + y * y + 1.0);
+  }
+  const double B = (double)dfilter_dist * std::sqrt(r2) + 1.0;
+  if (B_out) *B_out = B;
+  const double n = std::floor(2097152.0 / (B * B));
+  return n > 1e15 ? (long long)1e15 : (long long)n;
+}
+
 IcpPlan make_icp_plan(int levels, const LevelGeom *g, const int *iters, FrameView cur,
                       FrameView prev, float dist_thr, float angle_thr) {
   IcpPlan pl{};
@@ -3779,22 +3810,26 @@ bool icp_headroom(const IcpPlan &pl, int device, int cus_free) {
   return (long long)per_cu * (cus - cus_free) >= pl.nblocks;
 }
 
-bool icp_persistent_ok(IcpPlan &pl, int device) {
+bool icp_persistent_ok(IcpPlan &pl, int device, int block_cap, long long exact_pixels) {
   if (pl.slots > kIcpMaxSlots) return false;
   int per_cu = 0, cus = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_icp_track<false>, kIcpThreads, 0) != hipSuccess)
     return false;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
     return false;
+  // block_cap > 0 (kfx_debug_cap_icp_blocks): plan as if no more blocks than
+  // that were co-resident; a smaller grid than the device's own limit is
+  // co-resident all the more
+  const auto capped = [&](long long n) { return (int)(block_cap > 0 ? std::min<long long>(n, block_cap) : n); };
   pl.stride = 0;
-  if ((long long)per_cu * cus >= pl.nblocks) {
+  if (capped((long long)per_cu * cus) >= pl.nblocks) {
     return true;
   }
   // too many groups to be co-resident: the strided kernel on the blocks that are
   int per_cu_s = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, k_icp_track<true>, kIcpThreads, 0) != hipSuccess)
     return false;
-  const int cap = per_cu_s * cus;
+  const int cap = capped((long long)per_cu_s * cus);
   if (cap <= 0 || (pl.nblocks + cap - 1) / cap > kIcpStrideMax) return false;
   pl.nblocks = cap;
   pl.stride = 1;
@@ -3805,9 +3840,9 @@ bool icp_persistent_ok(IcpPlan &pl, int device) {
     if (pl.groups[l] <= cap) continue;
     const int per = (pl.npix[l] + cap - 1) / cap;
     const int span = (per + kIcpThreads - 1) / kIcpThreads * kIcpThreads;
-    // a block's fp64 sums of 2^-32-scaled products (|product| < 2^7) stay
-    // exact integers below 2^53 for up to 2^14 pixels: keep a margin of 2
-    if (span > 8 * kIcpPix * kIcpThreads) continue;
+    // one block's fp64 sums stay exact for exact_pixels pixels (icp_exact_pixels);
+    // a longer range takes whole 1024-pixel groups, each reduced on its own
+    if (span > exact_pixels) continue;
     pl.span[l] = span;
     pl.groups[l] = (pl.npix[l] + span - 1) / span;
   }

@@ -40,6 +40,7 @@ EXPORTS = [
     "kfx_extract_points_attr", "kfx_extract_mesh_attr", "kfx_write_ply_attr", "kfx_write_ply_mesh_attr",
     "kfx_save_pointcloud_attr", "kfx_save_mesh_attr",
     "kfx_debug_count_settled", "kfx_debug_get_settled",
+    "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
 ]
@@ -90,6 +91,8 @@ def lib():
         "kfx_debug_count_settled": ([vp, i], i),
         "kfx_debug_get_settled": ([vp, P(C.c_uint64)], i),
         "kfx_debug_icp_band_ms": ([vp, i, i, i, P(C.c_float)], i),
+        "kfx_debug_get_icp_sums": ([vp, P(C.c_int64)], i),
+        "kfx_debug_cap_icp_blocks": ([vp, i, P(C.c_int32)], i),
         "kfx_get_icp_trace": ([vp, P(C.c_uint64), i], i),
         "kfx_get_cur_camera_pose": ([vp, P(Pose)], i),
         "kfx_get_frame_count": ([vp, P(i)], i),
@@ -504,6 +507,29 @@ class KinectFusion:
         out = (C.c_uint64 * 2)()
         _check(lib().kfx_debug_get_settled(self._h, out), "kfx_debug_get_settled")
         return int(out[0]), int(out[1])
+
+    def debug_get_icp_sums(self) -> np.ndarray:
+        """The 27 int64 sums of the last ICP iteration that ran, whichever kernel ran it."""
+        s = np.zeros(27, np.int64)
+        _check(lib().kfx_debug_get_icp_sums(self._h, i64ptr(s)), "kfx_debug_get_icp_sums")
+        return s
+
+    def debug_cap_icp_blocks(self, cap: int = 0) -> dict:
+        """Plan the persistent ICP as if at most `cap` blocks were co-resident
+        (0: the device's own figure; < 0: change nothing); returns the plan in effect: usable,
+        stride, nblocks, launch (0 none, 1 plain, 2 cooperative) and per level
+        span / groups / ppl."""
+        a = (C.c_int32 * 16)()
+        r = lib().kfx_debug_cap_icp_blocks(self._h, int(cap), a)
+        _check(min(r, 0), "kfx_debug_cap_icp_blocks")
+        n = a[2]
+        return {"usable": bool(r), "stride": int(a[0]), "nblocks": int(a[1]), "launch": int(a[3]),
+                "span": [int(a[4 + 3 * l]) for l in range(n)], "groups": [int(a[5 + 3 * l]) for l in range(n)],
+                "ppl": [int(a[6 + 3 * l]) for l in range(n)]}
+
+    def debug_icp_plan(self) -> dict:
+        """The persistent ICP's plan in effect (debug_cap_icp_blocks without a change)."""
+        return self.debug_cap_icp_blocks(-1)
 
     def debug_icp_band_ms(self, rank, world, reps=5) -> float:
         """Device ms of the sharded ICP's launches for band rank of world (no

@@ -68,13 +68,15 @@ def test_create_argument_table(kfx_lib):
 
     def create(w, h, **kw):
         p = default_params(dims=64, range_m=2.048)
+        geo = {k: kw.pop(k) for k in ("fx", "fy", "cx", "cy") if k in kw}
         for k, v in kw.items():
             if k == "icp_iter_count":
                 for i, n in enumerate(v):
                     p.icp_iter_count[i] = n
             else:
                 setattr(p, k, v)
-        intr = Intrinsics(w, h, 0.8 * w, 0.8 * w, (w - 1) / 2.0, (h - 1) / 2.0)
+        intr = Intrinsics(w, h, geo.get("fx", 0.8 * w), geo.get("fy", geo.get("fx", 0.8 * w)),
+                          geo.get("cx", (w - 1) / 2.0), geo.get("cy", (h - 1) / 2.0))
         h_ = C.c_void_p()
         rc = L.kfx_create(C.byref(intr), C.byref(p), 0, C.byref(h_))
         if rc == 0:
@@ -93,6 +95,16 @@ def test_create_argument_table(kfx_lib):
         (320, 240, dict(icp_iter_count=[4, -1, 10, 0])),
         (320, 240, dict(pyramid_height=0)),
         (320, 240, dict(pyramid_height=5)),
+        # the ICP sums' exactness (icp_exact_pixels): the farthest vertex, 1 m of margin included, must stay
+        # below 45.25 m (a 1024-pixel block), and pixels x that bound squared below 2^31 (the int64 totals)
+        (320, 240, dict(dfilter_dist=30.0, fx=178.0)),              # corner at 45.04 m, 46.04 with margin
+        (2048, 2048, dict(dfilter_dist=17.0)),                      # 2^22 px x 23.7^2 m^2 >= 2^31
+        (320, 240, dict(icp_dist_threshold=1.5)),                   # the residual row entry would exceed the bound
+        (320, 240, dict(fx=0.0)),
+        (320, 240, dict(fx=-256.0)),
+        (320, 240, dict(fy=float("nan"))),
+        (320, 240, dict(cx=float("inf"))),
+        (320, 240, dict(cy=float("nan"))),
     ]
     for w, h, kw in rejected:
         assert create(w, h, **kw) == KFX_ERR_ARG, (w, h, kw)
@@ -106,6 +118,11 @@ def test_create_argument_table(kfx_lib):
         (320, 240, dict(dfilter_dist=30.0)),
         (320, 240, dict(bfilter_kernel_size=1)),
         (320, 240, dict(icp_iter_count=[0, 0, 0, 0])),
+        (320, 240, dict(dfilter_dist=30.0, fx=190.0)),              # corner at 43.48 m, 44.48 with margin
+        (2048, 2048, dict(dfilter_dist=15.0)),                      # 2^22 px x 21.0^2 m^2 < 2^31
+        (320, 240, dict(icp_dist_threshold=1.0)),
+        (320, 240, dict(icp_dist_threshold=-1.0)),                  # admits nothing: legal
+        (320, 240, dict(cx=-40.0, cy=300.0)),                       # a principal point outside the image is legal
     ]
     for w, h, kw in accepted:
         assert create(w, h, **kw) in (0, KFX_ERR_NO_DEVICE), (w, h, kw, L.kfx_last_error())
