@@ -2319,7 +2319,7 @@ int kfx_get_extract_ms(kfx_ctx *c, float out_ms[3]) {
 // the buffers cannot be allocated: the caller then runs the two-pass path.
 // per = 32-bit words per item (3 per point, 9 per triangle; attributed: 7 / 21).
 constexpr int64_t kExtractPoolItems = (int64_t)1 << 23;  // single-pass pool: <= 8.4 M items (100 MB of points)
-// words per item: kfx_vertex is 7 words (kfx_kernels.hip kVertexWords)
+// words per item: kfx_vertex is 7 words (kfx_extract.hip kVertexWords)
 static_assert(sizeof(kfx_vertex) == 28, "kfx_vertex is 7 32-bit words");
 static int extract_item_words(bool mesh, bool attr) { return (mesh ? 3 : 1) * (attr ? 7 : 3); }
 static int extract_single_pass(kfx_ctx *c, const uint8_t *tab, int zlo, int zhi, float *host, int64_t cap,

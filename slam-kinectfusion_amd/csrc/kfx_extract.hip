@@ -1,0 +1,576 @@
+// kfx_extract.hip — point-cloud and marching-cubes extraction (one sweep
+// kernel, pool copy, offset scans) and the rendered views of the model maps.
+// Compiled like kfx_kernels.hip (-ffp-contract=off, the reference's evaluation
+// order), so results are bit-identical to the CPU oracle.
+#include <algorithm>
+
+#include "kfx_device.h"
+
+#ifndef KFX_XSWEEP_WAVES
+#define KFX_XSWEEP_WAVES 65536  // extraction: units per wave grow (up to 64) while this many waves remain
+#endif
+
+namespace kfx {
+namespace {
+
+// ---------------------------------------------------------------------------
+// Point-cloud extraction — FullScan6 (tsdf_volume.cu:307-481): for every voxel
+// with W != 0 and F != 1 (A11: never 1), a zero crossing towards the +x, +y
+// and +z neighbour (W != 0, F != 1, opposite signs) gives the point
+// p = (V * |Fn| + Vn * |F|) / (|F| + |Fn|) along that edge, V the voxel
+// centre ((i + 0.5) * vs), transformed by the volume pose (R * p + t).
+//
+// The reference appends points with warp atomics (nondeterministic order, a
+// nondeterministic subset when the 10 M buffer fills).  Here the order is
+// canonical (D): wave = one 8x8 column tile x kExtractZ slices; points are
+// ordered by (slice chunk, tile, z, lane = (y&7)*8 + (x&7), edge x/y/z), so
+// the output and its first `cap` points are deterministic.  Pass 1 counts
+// per wave, a scan turns counts into offsets, pass 2 writes.
+constexpr int kExtractZ = 8;
+
+// ---- vertex attributes (kfx_extract_points_attr / kfx_extract_mesh_attr,
+// definitions: include/kfx.h) --------------------------------------
+// Gradient of F at voxel q = (x, y, z) (Fq = F(q)): per axis the difference of
+// the two neighbours, one-sided (doubled) when only one is valid, 0 when none
+// is.  Valid = inside the global volume and weight != 0.  A slab's owned items
+// read slices z - 1 .. z + 2 only: inside its kSlabHalo stored halo.
+__device__ __forceinline__ f3 tsdf_gradient(const VolView &v, int x, int y, int z, float Fq) {
+  float g[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int q = k == 0 ? x : (k == 1 ? y : z), dim = k == 0 ? v.X : (k == 1 ? v.Y : v.Z);
+    float hi = Fq, lo = Fq;
+    int valid = 0;
+    if (q + 1 < dim) {
+      const size_t j = vox_index(v, x + (k == 0), y + (k == 1), z + (k == 2));
+      if (v.weight[j] != 0) {
+        hi = (float)v.tsdf[j] * kDivShortMax;
+        ++valid;
+      }
+    }
+    if (q >= 1) {
+      const size_t j = vox_index(v, x - (k == 0), y - (k == 1), z - (k == 2));
+      if (v.weight[j] != 0) {
+        lo = (float)v.tsdf[j] * kDivShortMax;
+        ++valid;
+      }
+    }
+    float d = hi - lo;
+    if (valid == 1) d = d * 2.f;
+    g[k] = d / v.vs[k];
+  }
+  return {g[0], g[1], g[2]};
+}
+// The 4 attribute words {nx, ny, nz, b | g<<8 | r<<16 | a<<24} of the vertex on
+// the grid edge from voxel a = (x, y, z) to b = a + e_axis, written as integers
+// (the colour word is never a float).  Called by emitting lanes only: the
+// loads hit the bricks the wave has just read.
+__device__ __forceinline__ void vertex_attr(const VolView &v, const DevPose &aff, int x, int y, int z, int axis,
+                                            uint32_t *dst) {
+  const int xb = x + (axis == 0), yb = y + (axis == 1), zb = z + (axis == 2);
+  const size_t ia = vox_index(v, x, y, z), ib = vox_index(v, xb, yb, zb);
+  const int qa = v.tsdf[ia], qb = v.tsdf[ib];
+  const float Fa = (float)qa * kDivShortMax, Fb = (float)qb * kDivShortMax;
+  const f3 ga = tsdf_gradient(v, x, y, z, Fa), gb = tsdf_gradient(v, xb, yb, zb, Fb);
+  const float wa = fabsf(Fb), wb = fabsf(Fa);  // a's share is b's distance, as for the position
+  const f3 m = {ga.x * wa + gb.x * wb, ga.y * wa + gb.y * wb, ga.z * wa + gb.z * wb};
+  const f3 w = rmul(aff.R, m);
+  const float l = sqrtf(w.x * w.x + w.y * w.y + w.z * w.z);
+  f3 n = {0.f, 0.f, 0.f};
+  if (l != 0.f) n = {w.x / l, w.y / l, w.z / l};
+  const uint32_t ca = v.rgb[ia] & 0xffffffu, cb = v.rgb[ib] & 0xffffffu;
+  uint32_t col = 0u;
+  if (ca != 0u && cb != 0u) {
+    const uint32_t ta = (uint32_t)abs(qa), tb = (uint32_t)abs(qb), den = ta + tb;  // den > 0: a crossing
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      col |= ((((ca >> (8 * j)) & 0xffu) * tb + ((cb >> (8 * j)) & 0xffu) * ta + (den >> 1)) / den) << (8 * j);
+    col |= 0xff000000u;
+  } else if ((ca | cb) != 0u) {
+    col = (ca | cb) | 0xff000000u;
+  }
+  dst[0] = __float_as_uint(n.x);
+  dst[1] = __float_as_uint(n.y);
+  dst[2] = __float_as_uint(n.z);
+  dst[3] = col;
+}
+// words per attributed vertex (kfx_vertex)
+constexpr int kVertexWords = 7;
+__device__ __forceinline__ void st_vertex(uint32_t *dst, f3 p) {
+  dst[0] = __float_as_uint(p.x);
+  dst[1] = __float_as_uint(p.y);
+  dst[2] = __float_as_uint(p.z);
+}
+
+// axes (kAttr): the edge axis of point l in bits 2l, 2l + 1
+template <bool kAttr = false>
+__device__ __forceinline__ int extract_voxel(const VolView &v, const DevPose &aff, int x, int y,
+                                             int z, f3 (&pts)[3], int *axes = nullptr) {
+  const size_t i = vox_index(v, x, y, z);
+  const int W = v.weight[i];
+  const float F = (float)v.tsdf[i] * kDivShortMax;
+  if (W == 0 || F == 1.f) return 0;
+  const f3 V = {((float)x + 0.5f) * v.vs[0], ((float)y + 0.5f) * v.vs[1], ((float)z + 0.5f) * v.vs[2]};
+  const f3 t = {aff.t[0], aff.t[1], aff.t[2]};
+  int n = 0;
+  auto edge = [&](int axis, size_t j) {
+    const int Wn = v.weight[j];
+    const float Fn = (float)v.tsdf[j] * kDivShortMax;
+    if (Wn != 0 && Fn != 1.f && ((F > 0 && Fn < 0) || (F < 0 && Fn > 0))) {
+      f3 p = V;
+      const float Va = axis == 0 ? V.x : (axis == 1 ? V.y : V.z);
+      const float Vn = Va + v.vs[axis];
+      const float d_inv = 1.f / (fabsf(F) + fabsf(Fn));
+      const float c = (Va * fabsf(Fn) + Vn * fabsf(F)) * d_inv;
+      if (axis == 0) p.x = c;
+      else if (axis == 1) p.y = c;
+      else p.z = c;
+      if constexpr (kAttr) *axes |= axis << (2 * n);
+      pts[n++] = add(rmul(aff.R, p), t);
+    }
+  };
+  if (x + 1 < v.X) edge(0, vox_index(v, x + 1, y, z));
+  if (y + 1 < v.Y) edge(1, vox_index(v, x, y + 1, z));
+  edge(2, vox_index(v, x, y, z + 1));  // z + 1 < Z: guaranteed by the z range
+  return n;
+}
+
+// kEmit = false: counts[wave] = points of the wave; true: write them at
+// offsets[wave] + rank (rank < cap only).  z in [zlo, zhi) (global slices,
+// zhi <= Z - 1; a slab passes its owned range).
+// Extraction waves own one tile x one 8-slice chunk (kExtractZ), i.e. one
+// brick.  Every point needs a negative tsdf at the voxel or its +x/+y/+z
+// neighbour, and every marching-cubes triangle a negative corner: all of them
+// lie in the brick or a neighbouring one, so a clear (dilated) brick bit of
+// the occupancy map proves the wave outputs nothing — it reads no voxel.
+__device__ __forceinline__ bool brick_clear(const VolView &v, int tile, int c0) {
+  const int lbz = (c0 >> 3) - v.bz0;
+  if (lbz < 0 || lbz >= v.nbz) return false;
+  return !((v.bocc[(size_t)tile * v.bw + (lbz >> 6)] >> (lbz & 63)) & 1ull);
+}
+
+// One extraction wave's brick (lanes = the tile's 64 columns, slices [z0, z1)):
+// kEmit = false returns the wave's point count; true writes the points at
+// base + (canonical rank) (rank < cap only) and returns the count too.
+// kAttr (emit only): 7-word attributed points (kfx_vertex) instead of float3.
+template <bool kEmit, bool kAttr = false>
+__device__ __forceinline__ unsigned extract_wave(const VolView &v, const DevPose &aff, int x, int y, int z0,
+                                                 int z1, unsigned long long base, float *out,
+                                                 unsigned long long cap) {
+  const int lane = threadIdx.x & 63;
+  unsigned total = 0;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int z = z0; z < z1; ++z) {
+    f3 pts[3];
+    int axes = 0;
+    const int n = extract_voxel<kEmit && kAttr>(v, aff, x, y, z, pts, &axes);
+    const unsigned long long b1 = __ballot(n >= 1), b2 = __ballot(n >= 2), b3 = __ballot(n >= 3);
+    if (kEmit) {
+      const unsigned long long r = base + (unsigned long long)(__popcll(b1 & below) +
+                                                               __popcll(b2 & below) +
+                                                               __popcll(b3 & below));
+#pragma unroll
+      for (int l = 0; l < 3; ++l)  // (unrolled: pts stays in registers)
+        if (l < n && r + l < cap) {
+          if constexpr (kAttr) {
+            uint32_t *dst = reinterpret_cast<uint32_t *>(out) + (size_t)(r + l) * kVertexWords;
+            st_vertex(dst, pts[l]);
+            vertex_attr(v, aff, x, y, z, (axes >> (2 * l)) & 3, dst + 3);
+          } else {
+            st3(out, (size_t)(r + l), pts[l]);
+          }
+        }
+    }
+    const unsigned wt = (unsigned)(__popcll(b1) + __popcll(b2) + __popcll(b3));
+    base += wt;
+    total += wt;
+  }
+  return total;
+}
+
+// Marching cubes (§8 f5; C5 asks for a mesh, the reference has none).  Cube
+// (x, y, z) = the 8 voxels (x+dx, y+dy, z+dz); all 8 must have weight > 0;
+// corner c = dx | dy<<1 | dz<<2 is inside when its tsdf < 0.  `tab` (256 x
+// 16 bytes, built by the host, kfx_api.hip mc_table) lists per configuration
+// the triangles as edge indices (edge e: axis e/4, the 4 edges of an axis in
+// ascending lower-corner order).  An edge vertex interpolates the two voxel
+// centres as the point extraction does (FullScan6, tsdf_volume.cu:341-360),
+// then the volume pose.  Triangles come out in the canonical order of the
+// point cloud (8-slice chunk, tile, z, lane, triangle), 9 floats each.
+// kAttr: also writes the 7-word attributed vertex (kfx_vertex) to dst.
+template <bool kAttr = false>
+__device__ __forceinline__ f3 mc_vertex(const VolView &v, const DevPose &aff, int x, int y, int z, int e,
+                                        const float (&F)[8], uint32_t *dst = nullptr) {
+  const int a = e >> 2, k = e & 3;
+  // lower corner of edge e: the k-th corner (ascending) with bit a clear
+  int c = 0, m = 0;
+  for (int q = 0; q < 8; ++q)
+    if (!((q >> a) & 1)) {
+      if (m == k) c = q;
+      ++m;
+    }
+  const int cn = c | (1 << a);
+  f3 V = {((float)(x + (c & 1)) + 0.5f) * v.vs[0], ((float)(y + ((c >> 1) & 1)) + 0.5f) * v.vs[1],
+          ((float)(z + ((c >> 2) & 1)) + 0.5f) * v.vs[2]};
+  const float Fa = F[c], Fb = F[cn];
+  const float Va = a == 0 ? V.x : (a == 1 ? V.y : V.z);
+  const float Vn = Va + v.vs[a];
+  const float d_inv = 1.f / (fabsf(Fa) + fabsf(Fb));
+  const float cc = (Va * fabsf(Fb) + Vn * fabsf(Fa)) * d_inv;
+  if (a == 0) V.x = cc;
+  else if (a == 1) V.y = cc;
+  else V.z = cc;
+  const f3 p = add(rmul(aff.R, V), {aff.t[0], aff.t[1], aff.t[2]});
+  if constexpr (kAttr) {
+    st_vertex(dst, p);
+    vertex_attr(v, aff, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1), a, dst + 3);
+  }
+  return p;
+}
+
+// One marching-cubes wave's brick (as extract_wave): triangles in the
+// canonical order, 9 floats each.
+// kAttr (emit only): 21 words per triangle (3 kfx_vertex).
+template <bool kEmit, bool kAttr = false>
+__device__ __forceinline__ unsigned mesh_wave(const VolView &v, const DevPose &aff, const uint8_t *__restrict__ tab,
+                                              int x, int y, int z0, int z1, unsigned long long base, float *out,
+                                              unsigned long long cap) {
+  const int lane = threadIdx.x & 63;
+  unsigned total = 0;
+  for (int z = z0; z < z1; ++z) {
+    float F[8];
+    int cfg = 0, nt = 0;
+    if (x + 1 < v.X && y + 1 < v.Y) {
+      bool all = true;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const size_t i = vox_index(v, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1));
+        all = all && v.weight[i] > 0;
+        F[c] = (float)v.tsdf[i] * kDivShortMax;
+        cfg |= (F[c] < 0.f ? 1 : 0) << c;
+      }
+      if (all) nt = tab[16 * cfg];
+    }
+    // wave prefix of the triangle counts (lane order)
+    int incl = nt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(incl, off);
+      if (lane >= off) incl += o;
+    }
+    if (kEmit) {
+      const unsigned long long r0 = base + (unsigned long long)(incl - nt);
+      for (int t = 0; t < nt; ++t) {
+        if (r0 + t >= cap) break;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          if constexpr (kAttr)
+            (void)mc_vertex<true>(v, aff, x, y, z, tab[16 * cfg + 1 + 3 * t + k], F,
+                                  reinterpret_cast<uint32_t *>(out) + (size_t)(3 * (r0 + t) + k) * kVertexWords);
+          else
+            st3(out, (size_t)(3 * (r0 + t) + k), mc_vertex(v, aff, x, y, z, tab[16 * cfg + 1 + 3 * t + k], F));
+        }
+      }
+    }
+    const unsigned wt = (unsigned)__shfl(incl, 63);
+    base += wt;
+    total += wt;
+  }
+  return total;
+}
+
+// Extraction with ONE read of the volume (points or marching cubes).
+// Pass A (k_extract_pool): each canonical wave counts its brick's items and,
+// if it has any, reserves that many slots of a pool with one 64-bit atomic
+// (high bits: the wave's entry in the list of non-empty waves, low bits: the
+// pool offset) and writes its items there in its own canonical order (from
+// the bricks it just read: cache hits).  The reserved slots are unordered
+// across waves.  Then the offset scan of the per-wave counts (canonical
+// order) and pass C (k_extract_copy): one wave per listed wave copies its
+// items from the pool to their canonical position.  A pool too small for
+// every item (the caller's cap) sets *overflow; the counts are still complete,
+// and the host then runs the emit pass of the two-pass path instead.
+constexpr int kPoolListShift = 40;
+constexpr unsigned long long kPoolMask = (1ull << kPoolListShift) - 1ull;
+enum XMode { kXCount = 0, kXEmit = 1, kXPool = 2 };
+// The extraction passes.  A unit = one tile x one 8-slice chunk (the
+// canonical order's (chunk, tile)); each wave sweeps 64 consecutive units of
+// one chunk (K = 1..64, xsweep_units): lane l tests unit T0 + l's brick in
+// the occupancy map, a clear brick's unit has no items (count 0, no voxel
+// read), and the others are processed one after another by the whole wave
+// (lane = column).  At 2048^3 (16.8 M units, mostly clear) a wave per unit
+// is launch-bound (count pass 8.3 ms; 64 units per wave: 6.8 ms for count +
+// pool emit); small volumes keep enough waves with a small K.
+// kXCount: counts[unit]; kXEmit: items at offsets[unit] (first cap only);
+// kXPool: counts[unit] and the items into the pool (above).
+// kAttr (kXEmit / kXPool): attributed items, 7 words per point, 21 per
+// triangle, in place of 3 / 9 floats (the count pass needs no attributes).
+template <int kMode, bool kMesh, bool kAttr = false>
+__global__ __launch_bounds__(256) void k_xsweep(VolView v, DevPose aff, int zlo, int zhi,
+                                                const uint8_t *__restrict__ tab, unsigned *counts,
+                                                const unsigned long long *offsets, float *out,
+                                                unsigned long long cap, unsigned long long *ctr,
+                                                unsigned long long *pool_at, unsigned *list, unsigned *overflow,
+                                                int K) {
+  const int lane = threadIdx.x & 63;
+  const int ntiles = v.tiles_x * v.tiles_y;
+  const int T0 = (int)(blockIdx.x * 4 + (threadIdx.x >> 6)) * K;
+  if (T0 >= ntiles) return;
+  // chunks are aligned to global multiples of kExtractZ (slab boundaries are
+  // too), so concatenating slabs in rank order reproduces the single volume
+  const int c0 = (zlo / kExtractZ) * kExtractZ + (int)blockIdx.y * kExtractZ;
+  const int z0 = max(zlo, c0), z1 = min(zhi, c0 + kExtractZ);
+  static_assert(kExtractZ == 8, "one brick per unit");
+  const size_t ubase = (size_t)blockIdx.y * ntiles;  // unit index = ubase + tile
+  const int tl = T0 + lane;
+  const bool mine = lane < K && tl < ntiles;
+  const bool have = mine && !brick_clear(v, tl, c0);  // waves of clear bricks read nothing
+  if (kMode != kXEmit && mine && !have) counts[ubase + tl] = 0u;
+  unsigned long long work = __ballot(have);
+  while (work) {  // wave-uniform
+    const int t = __ffsll((long long)work) - 1;
+    work &= work - 1ull;
+    const int tile = T0 + t;
+    const size_t unit = ubase + tile;
+    const int x = (tile % v.tiles_x) * 8 + (lane & 7);
+    const int y = (tile / v.tiles_x) * 8 + (lane >> 3);
+    if (kMode == kXEmit) {
+      if (kMesh)
+        (void)mesh_wave<true, kAttr>(v, aff, tab, x, y, z0, z1, offsets[unit], out, cap);
+      else
+        (void)extract_wave<true, kAttr>(v, aff, x, y, z0, z1, offsets[unit], out, cap);
+      continue;
+    }
+    const unsigned n = kMesh ? mesh_wave<false>(v, aff, tab, x, y, z0, z1, 0ull, out, 0ull)
+                             : extract_wave<false>(v, aff, x, y, z0, z1, 0ull, out, 0ull);
+    if (lane == 0) counts[unit] = n;
+    if (kMode != kXPool || n == 0) continue;
+    unsigned long long old = 0;
+    if (lane == 0) old = atomicAdd(ctr, (1ull << kPoolListShift) | (unsigned long long)n);
+    old = __shfl(old, 0);
+    const unsigned long long base = old & kPoolMask;
+    if (lane == 0) {
+      list[old >> kPoolListShift] = (unsigned)unit;
+      pool_at[unit] = base;
+    }
+    if (base + n > cap) {  // (cap = the pool's size here)
+      if (lane == 0) atomicOr(overflow, 1u);
+      continue;
+    }
+    // the items again from the brick just read (cache hits; staging them in
+    // LDS during the count measured slower: occupancy)
+    if (kMesh)
+      (void)mesh_wave<true, kAttr>(v, aff, tab, x, y, z0, z1, base, out, cap);
+    else
+      (void)extract_wave<true, kAttr>(v, aff, x, y, z0, z1, base, out, cap);
+  }
+}
+// Pass C: listed wave i's items from the pool to offsets[wave] (first cap
+// items of the canonical order only); per = 32-bit words per item, copied as
+// integers (an attributed item's colour word is no float).
+__global__ __launch_bounds__(256) void k_extract_copy(const unsigned *__restrict__ list, unsigned nlist,
+                                                      const unsigned *__restrict__ counts,
+                                                      const unsigned long long *__restrict__ pool_at,
+                                                      const unsigned long long *__restrict__ offsets,
+                                                      const uint32_t *__restrict__ pool, uint32_t *out,
+                                                      unsigned long long cap, int per) {
+  const unsigned i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= nlist) return;
+  const int lane = threadIdx.x & 63;
+  const unsigned w = list[i];
+  const unsigned long long o = offsets[w];
+  if (o >= cap) return;
+  const unsigned long long n = min((unsigned long long)counts[w], cap - o);
+  const uint32_t *src = pool + pool_at[w] * per;
+  uint32_t *dst = out + o * per;
+  for (unsigned long long k = lane; k < n * per; k += 64) dst[k] = src[k];
+}
+
+// Exclusive scan of n u32 counts into u64 offsets (one 1024-thread block per
+// 4096 counts, then the block totals, then the fix-up); *total = the sum.
+__global__ __launch_bounds__(1024) void k_scan_local(const unsigned *in, unsigned long long *out,
+                                                     unsigned long long *bsum, size_t n) {
+  __shared__ unsigned long long s[1024];
+  const size_t b0 = (size_t)blockIdx.x * 4096 + threadIdx.x * 4;
+  unsigned long long v[4], acc = 0;
+  for (int k = 0; k < 4; ++k) {
+    v[k] = (b0 + k < n) ? in[b0 + k] : 0ull;
+    acc += v[k];
+  }
+  s[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan
+    const unsigned long long t = threadIdx.x >= off ? s[threadIdx.x - off] : 0ull;
+    __syncthreads();
+    s[threadIdx.x] += t;
+    __syncthreads();
+  }
+  unsigned long long run = s[threadIdx.x] - acc;
+  for (int k = 0; k < 4; ++k) {
+    if (b0 + k < n) out[b0 + k] = run;
+    run += v[k];
+  }
+  if (threadIdx.x == 1023) bsum[blockIdx.x] = s[1023];
+}
+__global__ __launch_bounds__(1024) void k_scan_blocks(unsigned long long *bsum, int nb,
+                                                      unsigned long long *total) {
+  // nb <= 1024 * 64: each thread scans a contiguous run, then one block scan
+  __shared__ unsigned long long s[1024];
+  const int per = (nb + 1023) / 1024;
+  const int b0 = threadIdx.x * per;
+  unsigned long long acc = 0;
+  for (int k = 0; k < per; ++k)
+    if (b0 + k < nb) acc += bsum[b0 + k];
+  s[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const unsigned long long t = threadIdx.x >= off ? s[threadIdx.x - off] : 0ull;
+    __syncthreads();
+    s[threadIdx.x] += t;
+    __syncthreads();
+  }
+  unsigned long long run = s[threadIdx.x] - acc;
+  for (int k = 0; k < per; ++k)
+    if (b0 + k < nb) {
+      const unsigned long long c = bsum[b0 + k];
+      bsum[b0 + k] = run;
+      run += c;
+    }
+  if (threadIdx.x == 1023) *total = s[1023];
+}
+__global__ void k_scan_add(unsigned long long *out, const unsigned long long *bsum, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] += bsum[i / 4096];
+}
+
+// kernel_renderNormals / kernel_renderPhong (image_process.cu:137-221) on the
+// previous frame's level-0 maps, lit from the last pose's camera position
+// (kinectfusion.cpp:33-47).  D as in the oracle (kfo_render): IEEE sqrt and
+// division in __m_normalize, pow(h, 10) as h8 * h2, NaN → 0 in the uchar
+// conversion; `0.5*light_coffi` stays double as in the source.
+__device__ __forceinline__ uint8_t render_u8(float x) { return x >= 1.f ? (uint8_t)fminf(x, 255.f) : 0; }
+__device__ __forceinline__ f3 normalized_ieee(f3 v) {
+  const float t = sqrtf(dot(v, v));
+  return {v.x / t, v.y / t, v.z / t};
+}
+__global__ __launch_bounds__(256) void k_render(const float *__restrict__ vmap, const float *__restrict__ nmap,
+                                                int n, const DevState *st, const DevPose *log, int type,
+                                                uint8_t *__restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const f3 nv = ld3(nmap, i), vv = ld3(vmap, i);
+  uint8_t o[3] = {0, 0, 0};
+  if (type == 1) {
+    o[0] = render_u8(fabsf(nv.x) * 255);
+    o[1] = render_u8(fabsf(nv.y) * 255);
+    o[2] = render_u8(fabsf(nv.z) * 255);
+  } else if (!(nv.x == 0 && nv.y == 0 && nv.z == 0) && !(vv.x == 0 && vv.y == 0 && vv.z == 0)) {
+    const DevPose &P = log[st->n_poses - 1];
+    const f3 kd = {0.3843f, 0.4745f, 0.580f};
+    const float intensity = 0.9f;
+    const f3 e = normalized_ieee(sub({P.t[0], P.t[1], P.t[2]}, vv));
+    const f3 l = normalized_ieee(sub({500.f, 500.f, -500.f}, vv));
+    float lc = dot(nv, l);
+    if (lc <= 0) lc = -lc;
+    float coef = intensity * lc;
+    const f3 diffuse = scl(kd, coef);
+    const f3 hv = normalized_ieee(add(l, e));
+    float hc = dot(nv, hv);
+    if (hc < 0) hc = -hc;
+    const float h2 = hc * hc, h4 = h2 * h2, h8 = h4 * h4;
+    coef = intensity * (h8 * h2);
+    const double spec = 0.5 * (double)coef;
+    o[0] = render_u8((float)fmin(1.0, (double)(0.1f + diffuse.x) + spec) * 255);
+    o[1] = render_u8((float)fmin(1.0, (double)(0.1f + diffuse.y) + spec) * 255);
+    o[2] = render_u8((float)fmin(1.0, (double)(0.1f + diffuse.z) + spec) * 255);
+  }
+  out[3 * (size_t)i] = o[0];
+  out[3 * (size_t)i + 1] = o[1];
+  out[3 * (size_t)i + 2] = o[2];
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// Launchers
+
+static int extract_chunks(int zlo, int zhi) {
+  if (zhi <= zlo) return 0;
+  const int a = (zlo / kExtractZ) * kExtractZ;
+  return (zhi - a + kExtractZ - 1) / kExtractZ;
+}
+size_t extract_waves(const VolView &v, int zlo, int zhi) {
+  return (size_t)v.tiles_x * v.tiles_y * (size_t)extract_chunks(zlo, zhi);
+}
+template <int kMode, bool kAttr = false>
+static void launch_xsweep(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
+                          unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap,
+                          unsigned long long *ctr, unsigned long long *pool_at, unsigned *list, unsigned *overflow) {
+  const int nc = extract_chunks(zlo, zhi);
+  if (nc == 0) return;
+  const int tiles = v.tiles_x * v.tiles_y;
+  // units per wave: as many as keep >= 64 K waves (at least 1, at most 64)
+  const size_t units = (size_t)tiles * nc;
+  int K = 1;
+  while (K < 64 && units / (size_t)(2 * K) >= (size_t)KFX_XSWEEP_WAVES) K *= 2;
+  dim3 grd((tiles + 4 * K - 1) / (4 * K), nc);  // 4 waves of K units per block
+  if (tab)
+    hipLaunchKernelGGL((k_xsweep<kMode, true, kAttr>), grd, dim3(256), 0, s, v, vpose, zlo, zhi, tab, counts, offsets,
+                       out, cap, ctr, pool_at, list, overflow, K);
+  else
+    hipLaunchKernelGGL((k_xsweep<kMode, false, kAttr>), grd, dim3(256), 0, s, v, vpose, zlo, zhi, tab, counts, offsets,
+                       out, cap, ctr, pool_at, list, overflow, K);
+}
+void launch_extract(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi,
+                    unsigned *counts, const unsigned long long *offsets, float *out,
+                    unsigned long long cap, bool attr) {
+  if (offsets && attr)
+    launch_xsweep<kXEmit, true>(s, v, vpose, zlo, zhi, nullptr, counts, offsets, out, cap, nullptr, nullptr, nullptr,
+                                nullptr);
+  else if (offsets)
+    launch_xsweep<kXEmit>(s, v, vpose, zlo, zhi, nullptr, counts, offsets, out, cap, nullptr, nullptr, nullptr, nullptr);
+  else
+    launch_xsweep<kXCount>(s, v, vpose, zlo, zhi, nullptr, counts, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+}
+void launch_mesh(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
+                 unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap,
+                 bool attr) {
+  if (offsets && attr)
+    launch_xsweep<kXEmit, true>(s, v, vpose, zlo, zhi, tab, counts, offsets, out, cap, nullptr, nullptr, nullptr,
+                                nullptr);
+  else if (offsets)
+    launch_xsweep<kXEmit>(s, v, vpose, zlo, zhi, tab, counts, offsets, out, cap, nullptr, nullptr, nullptr, nullptr);
+  else
+    launch_xsweep<kXCount>(s, v, vpose, zlo, zhi, tab, counts, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+}
+size_t scan_blocks(size_t n) { return (n + 4095) / 4096; }
+void launch_extract_pool(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
+                         unsigned *counts, unsigned long long *ctr, unsigned long long *pool_at, unsigned *list,
+                         float *pool, unsigned long long pool_cap, unsigned *overflow, bool attr) {
+  if (attr)
+    launch_xsweep<kXPool, true>(s, v, vpose, zlo, zhi, tab, counts, nullptr, pool, pool_cap, ctr, pool_at, list,
+                                overflow);
+  else
+    launch_xsweep<kXPool>(s, v, vpose, zlo, zhi, tab, counts, nullptr, pool, pool_cap, ctr, pool_at, list, overflow);
+}
+void launch_extract_copy(hipStream_t s, const unsigned *list, unsigned nlist, const unsigned *counts,
+                         const unsigned long long *pool_at, const unsigned long long *offsets, const float *pool,
+                         float *out, unsigned long long cap, int per) {
+  if (nlist == 0) return;
+  hipLaunchKernelGGL(k_extract_copy, dim3((nlist + 3) / 4), dim3(256), 0, s, list, nlist, counts, pool_at, offsets,
+                     reinterpret_cast<const uint32_t *>(pool), reinterpret_cast<uint32_t *>(out), cap, per);
+}
+void launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offsets,
+                 unsigned long long *bsum, size_t n, unsigned long long *total) {
+  const size_t nb = scan_blocks(n);
+  hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nb), dim3(1024), 0, s, counts, offsets, bsum, n);
+  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, bsum, (int)nb, total);
+  hipLaunchKernelGGL(k_scan_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, offsets, bsum, n);
+}
+
+void launch_render(hipStream_t s, const float *vmap, const float *nmap, int n, const DevState *st,
+                   const DevPose *log, int type, uint8_t *out) {
+  hipLaunchKernelGGL(k_render, dim3((n + 255) / 256), dim3(256), 0, s, vmap, nmap, n, st, log, type, out);
+}
+
+}  // namespace kfx

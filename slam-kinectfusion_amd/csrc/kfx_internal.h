@@ -1,5 +1,5 @@
-// kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip) and the
-// host runtime (kfx_api.hip).  Not part of the public ABI.
+// kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip,
+// kfx_extract.hip, kfx_volume_io.hip) and the host runtime (kfx_api.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -150,7 +150,7 @@ struct VolView {
   // leave the settled bookkeeping out.  Allocated with `settled`.
   unsigned *sgate;
   unsigned long long *skipcnt;  // kfx_debug_count_settled: bricks skipped by the last integrate (null: not counted)
-  // Integrate dispatch order (KFX_INT_LPT): iwork[tile] = the length of the
+  // Integrate dispatch order (k_int_order): iwork[tile] = the length of the
   // tile's wave-uniform z interval in the last integrate, iperm[b] = the
   // (chunk * tiles + tile) item block b runs (longest estimated first; any
   // permutation gives the same volume), inchunk = chunks per tile.
@@ -224,7 +224,8 @@ struct FrameView {
   float *n[kMaxLevels];
 };
 
-// ---- launchers (kfx_kernels.hip) -----------------------------------------
+// Launchers and host planning, by the file that defines them.
+// ---- kfx_kernels.hip (preprocess, ICP, integrate, raycast) -----------------
 // dl0: zero the frame's max-depth shards stored after that level-0 table
 void launch_frame_begin(hipStream_t s, DevState *st, float2 *dl0, LevelGeom g0);
 void launch_pyr_down(hipStream_t s, const float *src, const uint16_t *src16, int w, int h,
@@ -235,8 +236,7 @@ void launch_preprocess_maps(hipStream_t s, int levels, const float *const raw[kM
                             float sigma_color, float sigma_spatial, float max_dist,
                             const float *inv_lambda, float2 *dl0);
 int icp_blocks(const LevelGeom &g);
-// one ICP iteration (rigid_icp.cu:135-169 + icp_registration.cpp:33-42) in a
-// single launch; shards = 8 x 27 int64 zeroed, ticket zeroed (both self-reset)
+// the persistent kernel's plan: every level's pixels, groups and iterations
 IcpPlan make_icp_plan(int levels, const LevelGeom *g, const int *iters, FrameView cur,
                       FrameView prev, float dist_thr, float angle_thr);
 // grid co-resident + slots fit; block_cap > 0: as if at most that many blocks
@@ -254,6 +254,8 @@ bool icp_headroom(const IcpPlan &pl, int device, int cus_free);
 // back to per-iteration launches).
 hipError_t launch_icp_track(hipStream_t s, const IcpPlan &pl, DevState *st, IcpSync *sync, int begin = 0,
                             bool coop = false);
+// one ICP iteration (rigid_icp.cu:135-169 + icp_registration.cpp:33-42) in a
+// single launch; shards = 8 x 27 int64 zeroed, ticket zeroed (both self-reset)
 // band / nbands: only rows [ye*band/nbands, ye*(band+1)/nbands) of the
 // floor-covered region (a slab rank's share in the sharded ICP mode)
 void launch_icp(hipStream_t s, const LevelGeom &g, const float *cv, const float *cn,
@@ -298,21 +300,18 @@ void launch_raycast(hipStream_t s, VolView v, int levels, const LevelGeom *g, Fr
                     FrameView prev, const DevState *st, const DevPose *log, DevPose vpose,
                     const float *xpose, uint32_t *keys, unsigned long long *stats = nullptr,
                     const SlabPass &sp = SlabPass{}, unsigned *start_sig = nullptr, unsigned start_val = 0);
+// DevState::ray_kind / ray_c2v from the current tracking state, for a raycast
+// with no explicit pose that no pipeline integrate precedes
+void launch_ray_pose(hipStream_t s, DevState *st, const DevPose *log, DevPose vpose);
 // the reference raycast's distinct voxels read (out[0]) and reads (out[1]),
 // count-only (bits: one bit per stored voxel, workspace)
-void launch_ray_pose(hipStream_t s, DevState *st, const DevPose *log, DevPose vpose);
 void launch_raycast_touch(hipStream_t s, VolView v, LevelGeom g0, const DevState *st, const DevPose *log,
                           DevPose vpose, const float *xpose, uint32_t *bits, unsigned long long *out);
 // resizePointsNormals of levels >= 1 from the level-0 model maps
 void launch_resize(hipStream_t s, int levels, const LevelGeom *g, FrameView cur, FrameView prev,
                    const DevState *st, const float *xpose);
-// cross-slab combine: clear maps where the local key lost the MIN
-// out[0] += sum of per-voxel hashes, out[1] += voxels with weight > 0 (owned slices)
-void launch_checksum(hipStream_t s, VolView v, unsigned long long *out);
-// renderPhong (type 0) / renderNormals (type 1) of the level-0 maps into w*h uchar3
-void launch_render(hipStream_t s, const float *vmap, const float *nmap, int n, const DevState *st,
-                   const DevPose *log, int type, uint8_t *out);
-// keys = [key | Ts | nx | ny | nz] planes of the slab raycast (launch_raycast's keys)
+// cross-slab combine: clear the payload where the local key lost the MIN
+// keys = [key | pend | Ts | nx | ny | nz] planes of the slab raycast (launch_raycast's keys)
 void launch_slab_mask(hipStream_t s, const uint32_t *keys, const uint32_t *key_min, int n);
 // level-0 model maps from the combined payload (and the frame kind)
 void launch_slab_expand(hipStream_t s, LevelGeom g0, const uint32_t *pay, FrameView cur, FrameView prev,
@@ -326,6 +325,13 @@ void launch_inv_lambda(hipStream_t s, LevelGeom g0, float *inv_lambda);
 // device reads of mapped page-locked host memory into device buffers (two segments)
 void launch_host_fetch(hipStream_t s, const void *src0, void *dst0, size_t n0, const void *src1, void *dst1,
                        size_t n1);
+// z-chunks per column tile of k_integrate (the iperm item count is tiles x this)
+int integrate_chunks(const VolView &v);
+// per global slice: voxels passing integrate's depth test at vol2cam (an estimate, slab balancing)
+void launch_slice_work(hipStream_t s, const VolView &v, DevPose vol2cam, LevelGeom g0, const float2 *dl0,
+                       unsigned long long *hist);
+
+// ---- kfx_extract.hip ------------------------------------------------------
 // point extraction (FullScan6) over global slices [zlo, zhi): offsets == null
 // counts points per wave, else writes them (float3) at offsets (< cap).
 // attr (here and below): attributed items of 7 32-bit words per vertex
@@ -350,6 +356,11 @@ void launch_extract_copy(hipStream_t s, const unsigned *list, unsigned nlist, co
                          float *out, unsigned long long cap, int per);
 void launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offsets,
                  unsigned long long *bsum, size_t n, unsigned long long *total);
+// renderPhong (type 0) / renderNormals (type 1) of the level-0 maps into w*h uchar3
+void launch_render(hipStream_t s, const float *vmap, const float *nmap, int n, const DevState *st,
+                   const DevPose *log, int type, uint8_t *out);
+
+// ---- kfx_volume_io.hip ----------------------------------------------------
 void launch_export_records(hipStream_t s, VolView v, int z0, int nz, uint64_t *dst);
 void launch_import_records(hipStream_t s, VolView v, int z0, int nz, const uint64_t *src, unsigned *bad);
 void launch_export_soa(hipStream_t s, VolView v, int z0, int nz, int16_t *t, int16_t *w,
@@ -357,11 +368,8 @@ void launch_export_soa(hipStream_t s, VolView v, int z0, int nz, int16_t *t, int
 // clear the occupancy maps and re-mark every brick holding a negative tsdf
 // (after a volume upload)
 void launch_occ_rebuild(hipStream_t s, VolView v);
-// z-chunks per column tile of k_integrate (the iperm item count is tiles x this)
-int integrate_chunks(const VolView &v);
-// per global slice: voxels passing integrate's depth test at vol2cam (an estimate, slab balancing)
-void launch_slice_work(hipStream_t s, const VolView &v, DevPose vol2cam, LevelGeom g0, const float2 *dl0,
-                       unsigned long long *hist);
+// out[0] += sum of per-voxel hashes, out[1] += voxels with weight > 0 (owned slices)
+void launch_checksum(hipStream_t s, VolView v, unsigned long long *out);
 // owned-slice records of n (x, y) columns (device cols), column-major outputs
 void launch_gather_columns(hipStream_t s, VolView v, const int32_t *cols, int n, int16_t *t, int16_t *w,
                            uint32_t *c);

@@ -54,7 +54,7 @@ _lib = None
 
 
 def build() -> str:
-    subprocess.run(["make", "-s", "-C", _PKG], check=True)
+    subprocess.run(["make", "-s", "-j8", "-C", _PKG], check=True)
     return LIB_PATH
 
 

@@ -1,9 +1,10 @@
-"""tools/sqrt_bound_check.cpp checks a copy of sqrt_le_bound: the copy is
-textually the function in kfx_kernels.hip, and the tool, built plain and with
-UBSan as a stand-alone binary, finds (sqrtf(x) <= t) == (x <= bound(t)) over
-every 4099th non-negative float (inf and NaNs included) and the 64 floats on
-either side of each bound."""
+"""tools/sqrt_bound_check.cpp checks the library's own sqrt_le_bound: it
+includes csrc/kfx_sqrtbound.h (as the ICP's kernel file does) and defines no copy, and
+the tool, built plain and with UBSan as a stand-alone binary, finds
+(sqrtf(x) <= t) == (x <= bound(t)) over every 4099th non-negative float (inf
+and NaNs included) and the 64 floats on either side of each bound."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -11,18 +12,25 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "tools", "sqrt_bound_check.cpp")
-KERNELS = os.path.join(ROOT, "slam-kinectfusion_amd", "csrc", "kfx_kernels.hip")
+CSRC = os.path.join(ROOT, "slam-kinectfusion_amd", "csrc")
 
 
-def body(path):
-    src = open(path).read()
-    a = src.index("float sqrt_le_bound(float t) {")
-    return src[a:src.index("\n}\n", a) + 3]
-
-
-def test_tool_checks_the_kernel_files_function():
-    assert body(TOOL) == body(KERNELS)
-    assert "std::nextafter" in body(TOOL) and body(TOOL).count("\n") > 10
+def test_tool_checks_the_librarys_function():
+    tool = open(TOOL).read()
+    inc = re.search(r'^#include "(.*kfx_sqrtbound\.h)"', tool, re.M)
+    assert inc, "the tool includes the header"
+    header = os.path.normpath(os.path.join(os.path.dirname(TOOL), inc.group(1)))
+    assert header == os.path.join(CSRC, "kfx_sqrtbound.h")
+    assert not re.search(r"\bsqrt_le_bound\s*\(\s*float\b", tool), "the tool defines no copy"
+    # the one definition, shared with the ICP plan
+    body = open(header).read()
+    assert len(re.findall(r"\bsqrt_le_bound\s*\(\s*float\b", body)) == 1
+    assert "std::nextafter" in body
+    assert any(f.endswith(".hip") and '#include "kfx_sqrtbound.h"' in open(os.path.join(CSRC, f)).read()
+               for f in os.listdir(CSRC)), "the ICP's kernel file includes the header"
+    others = [f for f in os.listdir(CSRC) if f != "kfx_sqrtbound.h"
+              and re.search(r"\bsqrt_le_bound\s*\(\s*float\b", open(os.path.join(CSRC, f)).read())]
+    assert others == []
 
 
 @pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=all"]],

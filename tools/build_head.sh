@@ -1,13 +1,23 @@
 #!/bin/bash
-# build the committed (HEAD) library as lib/var_head for A/B runs against the working tree
+# build a committed revision's library as lib/var_head, for A/B runs against the
+# working tree, and its device assembly as lib/var_head/asm/<file>.s (for
+# tools/isa_same.py), with that revision's own Makefile, flags and file set:
+#   tools/build_head.sh [rev, default HEAD] [EXTRA flags...]
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
+REV=${1:-HEAD}
+[ $# -gt 0 ] && shift
 T=$(mktemp -d)
-mkdir -p "$T/include" "$T/slam-kinectfusion_amd/csrc" "$T/slam-kinectfusion_amd/examples"
-git -C "$R" show HEAD:include/kfx.h > "$T/include/kfx.h"
-for f in Makefile csrc/kfx_kernels.hip csrc/kfx_api.hip csrc/kfx_dataset.cpp csrc/kfx_internal.h csrc/kfx_ffadd.h csrc/kfx_raystep.h examples/kfx_run.cpp; do
-  git -C "$R" show "HEAD:slam-kinectfusion_amd/$f" > "$T/slam-kinectfusion_amd/$f"
-done
-make -C "$T/slam-kinectfusion_amd" -j8 OUT="$R/slam-kinectfusion_amd/lib/var_head" "$R/slam-kinectfusion_amd/lib/var_head/libkfx.so" EXTRA="$*" > /dev/null
-rm -rf "$T"
-echo "built lib/var_head"
+trap 'rm -rf "$T"' EXIT
+git -C "$R" archive "$REV" include slam-kinectfusion_amd | tar -x -C "$T"
+S=$T/slam-kinectfusion_amd
+O=$R/slam-kinectfusion_amd/lib/var_head
+rm -rf "$O"  # objects of another revision would pass for current (archive files carry the commit's time)
+make -C "$S" -j8 OUT="$O" "$O/libkfx.so" EXTRA="$*" > /dev/null
+if make -C "$S" -n OUT="$O" EXTRA="$*" asm > /dev/null 2>&1; then
+  make -C "$S" -j8 OUT="$O" EXTRA="$*" asm > /dev/null
+else  # a revision from before the asm target: this tree's rule, on that revision's HIPCC and HIPFLAGS
+  make -C "$S" -j8 OUT="$O" EXTRA="$*" asm --eval='asm: $(patsubst csrc/%.hip,$(OUT)/asm/%.s,$(wildcard csrc/*.hip))
+$(OUT)/asm/%.s: csrc/%.hip ; @mkdir -p $(OUT)/asm && $(HIPCC) $(HIPFLAGS) --cuda-device-only -S $< -o $@' > /dev/null
+fi
+echo "built lib/var_head from $REV"

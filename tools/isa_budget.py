@@ -1,19 +1,17 @@
 #!/usr/bin/env python3
 """Per-basic-block instruction budget of the shipped k_integrate<false, true>
 main loop (VALU / SALU / memory per block, in code order), from the gfx950
-assembly of csrc/kfx_kernels.hip.  usage: tools/isa_budget.py [out.txt]"""
+assembly the Makefile's own flags give (make lib/asm/kfx_kernels.s).
+usage: tools/isa_budget.py [out.txt]"""
 import collections
 import os
 import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "slam-kinectfusion_amd", "csrc", "kfx_kernels.hip")
-asm = "/tmp/kfx_isa_budget.s"
-subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
-                "-fno-fast-math", "--cuda-device-only", "-S", src, "-o", asm], check=True, capture_output=True)
-text = open(asm).read()
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "slam-kinectfusion_amd")
+subprocess.run(["make", "-s", "-C", PKG, "lib/asm/kfx_kernels.s"], check=True, capture_output=True)
+text = open(os.path.join(PKG, "lib", "asm", "kfx_kernels.s")).read()
 m = [x for x in re.finditer(r"^(_ZN3kfx\S+):\s", text, re.M) if "k_integrateILb0ELb1EE" in x.group(1)][0]
 body = text[m.end():text.find(".Lfunc_end", m.end())].splitlines()
 # the main loop: the loop whose blocks hold the depth gathers (buffer_load_dwordx2)

@@ -1,13 +1,12 @@
 #!/usr/bin/env python3
-"""Tabulate hipcc -Rpass-analysis=kernel-resource-usage for a HIP source."""
+"""Tabulate the kernel-resource-usage remarks of the shipped kernels (the
+Makefile's resource-usage target: every csrc/*.hip with the library's flags)."""
+import os
 import re
 import subprocess
-import sys
 
-src = sys.argv[1] if len(sys.argv) > 1 else "slam-kinectfusion_amd/csrc/kfx_kernels.hip"
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
-       "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "slam-kinectfusion_amd")
+out = subprocess.run(["make", "-s", "-C", PKG, "resource-usage"], capture_output=True, text=True, check=True).stdout
 rows, cur = {}, None
 for line in out.splitlines():
     m = re.search(r"remark:\s+(.*?):\s+(.*?) \[-Rpass", line)

@@ -1,5 +1,5 @@
-// Exhaustive check of sqrt_le_bound (kfx_kernels.hip, a copy of the host function
-// below): for every non-negative float x, (sqrtf(x) <= t) == (x <= bound(t)).
+// Exhaustive check of sqrt_le_bound (csrc/kfx_sqrtbound.h, the function the ICP
+// plan calls): for every non-negative float x, (sqrtf(x) <= t) == (x <= bound(t)).
 // build: g++ -O2 -ffp-contract=off tools/sqrt_bound_check.cpp -o /tmp/sqrt_bound_check
 // usage: sqrt_bound_check [stride]   (every stride-th float, default 1, and always the 64 floats on either
 // side of each bound; exit status 1 on a mismatch)
@@ -9,20 +9,9 @@
 #include <cstdint>
 #include <cstdlib>
 #include <limits>
-float sqrt_le_bound(float t) {
-  if (std::isnan(t)) return t;
-  if (t < 0.f) return -1.f;
-  if (std::isinf(t)) return t;
-  float x = t * t;
-  if (std::isinf(x)) x = std::numeric_limits<float>::max();
-  while (x > 0.f && std::sqrt(x) > t) x = std::nextafter(x, 0.f);
-  for (;;) {
-    const float n = std::nextafter(x, std::numeric_limits<float>::infinity());
-    if (std::isinf(n) || std::sqrt(n) > t) break;
-    x = n;
-  }
-  return x;
-}
+
+#include "../slam-kinectfusion_amd/csrc/kfx_sqrtbound.h"
+using kfx::sqrt_le_bound;
 int main(int argc, char **argv) {
   const uint64_t stride = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 1;
   if (stride == 0) return 2;
