@@ -16,6 +16,7 @@
 
 #include "../../include/kfx.h"
 #include "kfx_internal.h"
+#include "kfx_settled.h"
 
 using namespace kfx;
 
@@ -1191,6 +1192,7 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
   for (float2 *&d : c->dl0b)
     if ((r = dalloc(c, (void **)&d, np0 * 8 + 64 + grid16 * 8))) return fail(r);  // (+ the min-depth grid)
   c->vol = make_vol(p, rank, world, cuts);
+  c->vol.far_k = far_clip_factor(intr->fx, intr->fy);
   // raycast wave durations of the last frame (4 waves per 16x16 block; zeroed: no hint)
   if ((r = dalloc(c, (void **)&c->vol.rdur, grid16 * 4 * sizeof(unsigned)))) return fail(r);
   const size_t n = nvox(c);

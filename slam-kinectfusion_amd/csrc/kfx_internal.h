@@ -126,6 +126,7 @@ struct VolView {
   float range[3];  // volume_range
   float trunc;
   float inv_trunc;  // RN(1/trunc), for the exact FMA division (kfx_kernels.hip div_rn)
+  float far_k;      // far_clip_factor of the level-0 intrinsics (kfx_settled.h): integrate's far clips and certificate
   size_t slice;    // voxels per z slice (= X*Y)
   // Dilated occupancy of negative tsdf (raycast empty-space skipping, DESIGN.md
   // §4): bit set <=> some voxel within one brick of this brick may hold a

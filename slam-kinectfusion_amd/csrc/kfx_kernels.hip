@@ -1399,7 +1399,7 @@ __device__ __forceinline__ void int_column(const VolView &v, const LevelGeom &g,
     clip_lin(cxh * az - g.fx * ax, cxh * sz - g.fx * sx, lo, hi);
     clip_lin(g.fy * ay + cyl * az, g.fy * sy + cyl * sz, lo, hi);
     clip_lin(cyh * az - g.fy * ay, cyh * sz - g.fy * sy, lo, hi);
-    const float zfar = (dmax + v.trunc) * 1.02f + 0.01f;
+    const float zfar = (dmax + v.trunc) * v.far_k + 0.01f;  // far_clip_factor (kfx_settled.h)
     clip_lin(zfar - az, -sz, lo, hi);
   }
   zl = INT_MAX, zh = INT_MIN;
@@ -1412,9 +1412,10 @@ __device__ __forceinline__ void int_column(const VolView &v, const LevelGeom &g,
 
 // Occlusion clip of a column tile's intervals.  A voxel can
 // only be updated where its pixel's depth d satisfies d - il |vc| >= -trunc
-// (tsdf_volume.cu:67-71), and il |vc| >= vc.z / 1.0011 for every in-image
-// voxel, so no voxel with vc.z > (D + trunc) * 1.0011 is updated when D bounds
-// the depth of every pixel it can project to.  The lanes' segments (linear vc
+// (tsdf_volume.cu:67-71), and il |vc| >= vc.z (1 - delta) for every in-image
+// voxel (delta: half a pixel's worth of ray length, far_clip_factor in
+// kfx_settled.h), so no voxel with vc.z > (D + trunc) * far_k is updated when D
+// bounds the depth of every pixel it can project to.  The lanes' segments (linear vc
 // model, as int_column) project into a pixel box; with 2 pixels of margin it
 // covers every rounded projection, and when it spans at most kOcclCells cells
 // of the frame's 16x16-pixel max-depth grid, D = their max replaces the
@@ -1467,7 +1468,7 @@ __device__ __forceinline__ void int_tile_clip(const VolView &v, const LevelGeom 
   (void)nby;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) dm = max(dm, (unsigned)__shfl_xor((int)dm, off));
-  const float zfar = (__uint_as_float(dm) + v.trunc) * 1.02f + 0.01f;
+  const float zfar = (__uint_as_float(dm) + v.trunc) * v.far_k + 0.01f;
   if (own) {
     float lo = (float)zl, hi = (float)zh;
     clip_lin(zfar - vc0.z, -zs.z, lo, hi);
@@ -1672,7 +1673,7 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
       for (int i = 0; i < 9; ++i) Q.R[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_pose.R[i])));
       for (int i = 0; i < 3; ++i) Q.t[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_pose.t[i])));
       const bool cert = set && brick_certified(Q.R, Q.t, v.vs[0], v.vs[1], g.fx, g.fy, g.cx, g.cy, g.w, g.h, x & ~7,
-                                               y & ~7, gb * 8, v.trunc, dmin_grid(dl, g), (g.w + 15) >> 4);
+                                               y & ~7, gb * 8, v.trunc, dmin_grid(dl, g), (g.w + 15) >> 4, v.far_k);
       skipm = __ballot(cert);
     }
   }

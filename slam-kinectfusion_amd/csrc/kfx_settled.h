@@ -18,28 +18,67 @@
 //     focal length keeps that drift (< 0.1 voxel) below one pixel.
 //   * Dmin = the least positive depth of the grid cells under the box bounds
 //     the depth d of each such pixel from below (+inf: none has depth).
-//   * For an in-image voxel il |vc| <= vc.z * 1.0011 (il = 1 / lambda of its
-//     pixel), and vc.z <= pzmax + 2 voxels (the linear model's largest corner
-//     plus the drift margin), so
-//       sdf = d - il |vc| >= Dmin - 1.0011 (pzmax + 2 vs).
-//     Certified when Dmin >= (pzmax + 2 vs + trunc) * 1.02 + 0.01 (the far
-//     clip's form): then sdf >= 1.02 trunc + 0.01, so tq = RN(sdf / trunc) >= 1
-//     and sdf > trunc / 2 with a margin far above the few ulps of the device's
-//     sdf arithmetic.
+//   * For an in-image voxel il |vc| <= vc.z (1 + delta) (il = 1 / lambda of
+//     its pixel; far_clip_factor below), and vc.z <= pzmax + 2 voxels (the
+//     linear model's largest corner plus the drift margin), so
+//       sdf = d - il |vc| >= Dmin - (1 + delta) (pzmax + 2 vs).
+//     Certified when Dmin >= (pzmax + 2 vs + trunc) * far_k + 0.01 (the far
+//     clip's form; far_k >= 1.02 and far_k >= 1.001 (1 + delta)): then
+//     sdf >= 1.02 trunc + 0.01, so tq = RN(sdf / trunc) >= 1 and
+//     sdf > trunc / 2 with a margin far above the few ulps of the device's
+//     sdf arithmetic.  (far_k = +inf, a camera too coarse for any bound,
+//     certifies only a brick none of whose pixels has depth.)
 // Any NaN makes a comparison false: not certified.  Host and device share
 // this text (tests/settled/settled_check.cpp).
 #pragma once
+#include <cmath>
+
 #include "kfx_ffadd.h"
 
 namespace kfx {
 
+// How far |vc| / lambda can lie from vc.z, and the factor integrate's far
+// clips (int_column, int_tile_clip) and the certificate below derive from it.
+//
+// A voxel at vc (vc.z > 0) is tested against the pixel (u, v) its projection
+// rounds to, with lambda = |p|, p = ((u - cx) / fx, (v - cy) / fy, 1), while
+// |vc| = vc.z |r| with r = (vc.x / vc.z, vc.y / vc.z, 1) its own ray.  Rounding
+// moves the projection by at most half a pixel per axis, so
+// |r - p| <= delta = hypot(1 / fx, 1 / fy) / 2, hence ||r| - |p|| <= delta, and
+// with |p| >= 1
+//     |vc| / lambda = vc.z |r| / |p|  lies in  vc.z [1 - delta, 1 + delta]
+// for every voxel whose pixel is in the image (the same at every pixel: the
+// bound does not depend on cx, cy or the image size).
+//
+// A voxel is updated only when d - |vc| / lambda >= -trunc, d its pixel's
+// depth: with D >= d that needs vc.z (1 - delta) <= D + trunc.  No voxel with
+//     vc.z > (D + trunc) * far_k,   far_k = max(1.02, 1.001 / (1 - delta)),
+// is updated (the clips add 0.01 m on top).  1.001 leaves a thousand times the
+// rounding of the float evaluation of sdf; 1.02 is the value every camera with
+// fx, fy >= 38 px keeps (delta <= 0.0187), among them every benchmark camera.
+// Below that the half pixel is worth more than 2 %: at fx = fy = 9.6 px the
+// factor is 1.0806.  For delta >= 0.5 (fx, fy of about 1.4 px and less) no
+// bound of this kind holds: +inf, which switches the far clips and the
+// certificate off.  A launch-time constant of the level-0 intrinsics
+// (VolView::far_k), not loop code.
+KFX_HD inline float far_clip_delta(float fx, float fy) {
+  return 0.5f * std::sqrt(1.f / (fx * fx) + 1.f / (fy * fy));
+}
+KFX_HD inline float far_clip_factor(float fx, float fy) {
+  const float delta = far_clip_delta(fx, fy);
+  if (!(delta < 0.5f)) return INFINITY;  // (NaN too)
+  const float k = 1.001f / (1.f - delta);
+  return k > 1.02f ? k : 1.02f;
+}
+
 constexpr int kSettledMaxCells = 36;  // a larger pixel box: not certified
 
 // dmin: the min-depth grid (float bits, +inf bits for a cell without depth),
-// nbx cells per row; (x0, y0, z0) the brick's first voxel
+// nbx cells per row; (x0, y0, z0) the brick's first voxel; far_k =
+// far_clip_factor of the level-0 intrinsics
 KFX_HD inline bool brick_certified(const float *R, const float *t, float vs0, float vs1, float fx, float fy, float cx,
                                    float cy, int w, int h, int x0, int y0, int z0, float trunc, const unsigned *dmin,
-                                   int nbx) {
+                                   int nbx, float far_k) {
   const float zsx = R[2] * vs0, zsy = R[5] * vs0, zsz = R[8] * vs0;
   const float pzmin = 0.1f * vs0 * (fx > fy ? fx : fy);
   float umin = 0.f, umax = 0.f, vmin = 0.f, vmax = 0.f, pzmax = 0.f;
@@ -79,8 +118,17 @@ KFX_HD inline bool brick_certified(const float *R, const float *t, float vs0, fl
     }
   float Dmin;
   std::memcpy(&Dmin, &dm, 4);
-  const float need = (pzmax + 2.f * vs0 + trunc) * 1.02f + 0.01f;
+  const float need = (pzmax + 2.f * vs0 + trunc) * far_k + 0.01f;
   return Dmin >= need;
+}
+
+// The same with far_k derived here from the focal lengths (callers that hold
+// no launch constant: host checks).
+KFX_HD inline bool brick_certified(const float *R, const float *t, float vs0, float vs1, float fx, float fy, float cx,
+                                   float cy, int w, int h, int x0, int y0, int z0, float trunc, const unsigned *dmin,
+                                   int nbx) {
+  return brick_certified(R, t, vs0, vs1, fx, fy, cx, cy, w, h, x0, y0, z0, trunc, dmin, nbx,
+                         far_clip_factor(fx, fy));
 }
 
 }  // namespace kfx

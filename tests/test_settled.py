@@ -9,7 +9,16 @@ and bricks (anywhere, a few centimetres in front of a surface, across the
 image border) and evaluates every voxel of each certified brick with the
 oracle's arithmetic; one voxel updated with ts < 1 or in the colour band fails
 the run, and so does a run that certified no brick of one of the kinds.  Built
-plain (-O2, no contraction) and, on fewer cases, under ASan + UBSan."""
+plain (-O2, no contraction) and, on fewer cases, under ASan + UBSan.
+
+test_certificate_wider_draws runs the program's other draw modes under both
+builds: the volume turned by up to 1.2 rad about x and y, anisotropic voxels,
+images of 16x16 .. 64x48 pixels at fx = 0.3 .. 0.6 w, a directed wide-angle
+draw (a far brick whose pixel box reaches the image border, a wall at the
+least depth the certificate accepts), and a brute-force check of the bound
+|vc| / lambda in vc.z [1 - delta, 1 + delta] that the certificate and
+integrate's far clips share (kfx::far_clip_factor).  With the factor fixed at
+1.02 the directed draw fails at seeds 3 and 4 and the bound check at seed 1."""
 import os
 import re
 import shutil
@@ -22,16 +31,23 @@ SRC = os.path.join(ROOT, "tests", "settled", "settled_check.cpp")
 INC = os.path.join(ROOT, "slam-kinectfusion_amd", "csrc")
 
 
-@pytest.mark.parametrize("flags,seeds,cases", [
-    (["-O2"], (1, 2, 3), 150),
-    (["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], (4,), 40),
-], ids=["O2", "asan_ubsan"])
+BUILDS = {
+    "O2": (["-O2"], (1, 2, 3), 150),
+    "asan_ubsan": (["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], (4,), 40),
+}
+
+
+def compile_check(exe, flags):
+    subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", *flags, "-I", INC, SRC, "-o", exe],
+                   check=True)
+
+
+@pytest.mark.parametrize("flags,seeds,cases", list(BUILDS.values()), ids=list(BUILDS))
 def test_certified_bricks_need_no_update(tmp_path, flags, seeds, cases):
     if shutil.which("g++") is None:
         pytest.skip("no g++")
     exe = str(tmp_path / "settled_check")
-    subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", *flags, "-I", INC, SRC, "-o", exe],
-                   check=True)
+    compile_check(exe, flags)
     for seed in seeds:
         r = subprocess.run([exe, str(seed), str(cases)], capture_output=True, text=True, timeout=300)
         m = re.search(r"bad (\d+) certified (\d+) of (\d+) near (\d+) edge (\d+)", r.stdout)
@@ -40,3 +56,38 @@ def test_certified_bricks_need_no_update(tmp_path, flags, seeds, cases):
         print(f"seed {seed}: certified {cert} of {total} bricks ({100.0 * cert / total:.1f} %), "
               f"{near} beside a surface, {edge} across the image border")
         assert r.returncode == 0 and bad == 0 and cert > 0 and near > 0 and edge > 0, r.stdout[-2000:]
+
+
+@pytest.fixture(scope="module")
+def executables(tmp_path_factory):
+    """settled_check under each build, compiled once for all modes."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    out = {}
+    for name, (flags, _, _) in BUILDS.items():
+        out[name] = str(tmp_path_factory.mktemp("settled_" + name) / "settled_check")
+        compile_check(out[name], flags)
+    return out
+
+
+@pytest.mark.parametrize("mode", ["rot", "aniso", "small", "wide", "bound"])
+@pytest.mark.parametrize("build", list(BUILDS))
+def test_certificate_wider_draws(executables, build, mode):
+    _, seeds, cases = BUILDS[build]
+    for seed in (seeds if mode in ("wide", "bound") else seeds[:1]):
+        r = subprocess.run([executables[build], str(seed), str(cases), mode], capture_output=True, text=True,
+                           timeout=300)
+        if mode == "bound":
+            m = re.search(r"bound bad (\d+) checked (\d+)", r.stdout)
+            assert m, (r.stdout[-2000:], r.stderr[-2000:])
+            bad, checked = map(int, m.groups())
+            assert r.returncode == 0 and bad == 0 and checked >= 4000 * cases, r.stdout[-2000:]
+            continue
+        m = re.search(r"bad (\d+) certified (\d+) of (\d+) near (\d+) edge (\d+)", r.stdout)
+        assert m, (r.stdout[-2000:], r.stderr[-2000:])
+        bad, cert, total, near, edge = map(int, m.groups())
+        print(f"{mode} seed {seed}: certified {cert} of {total} bricks, {near} beside a surface, "
+              f"{edge} across the image border")
+        assert r.returncode == 0 and bad == 0 and cert >= cases // 2, r.stdout[-2000:]
+        if mode != "wide":
+            assert near > 0 and edge > 0
