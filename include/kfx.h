@@ -188,6 +188,12 @@ int kfx_debug_force_index64(kfx_ctx *ctx, int on);
  * count is off).  Results are identical with the count on or off. */
 int kfx_debug_count_settled(kfx_ctx *ctx, int on);
 int kfx_debug_get_settled(kfx_ctx *ctx, uint64_t out[2]);
+/* Debug count of integrate's hidden-brick skip (added under ABI
+ * version 2, nothing else changed), armed by kfx_debug_count_settled: out[0] =
+ * bricks the last integrate launch stepped over as hidden behind every surface
+ * they project onto, out[1] = those among them that hang over an end of their
+ * tile's interval (both 0 while the count is off). */
+int kfx_debug_get_hidden(kfx_ctx *ctx, uint64_t out[2]);
 /* Debug hooks of the ICP reduction (added under ABI version 2,
  * nothing else changed).  kfx_debug_get_icp_sums: the 27 int64 fixed-point
  * sums (kfx_stage_icp_accumulate's layout) of the last ICP iteration that ran

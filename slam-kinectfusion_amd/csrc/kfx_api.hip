@@ -162,7 +162,7 @@ struct kfx_ctx {
   // above alias set `par`, the one the last frame used.
   FrameView curb[2]{};
   float2 *dl0b[2]{};
-  unsigned long long *skipcnt = nullptr;  // VolView::skipcnt's word (kfx_debug_count_settled)
+  unsigned long long *skipcnt = nullptr;  // VolView::skipcnt's three words (kfx_debug_count_settled)
   IcpPlan planb[2]{};
   int par = 0;
   bool overlap = true;
@@ -1193,6 +1193,7 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
     if ((r = dalloc(c, (void **)&d, np0 * 8 + 64 + grid16 * 8))) return fail(r);  // (+ the min-depth grid)
   c->vol = make_vol(p, rank, world, cuts);
   c->vol.far_k = far_clip_factor(intr->fx, intr->fy);
+  c->vol.hid_k = hidden_clip_factor(intr->fx, intr->fy);
   // raycast wave durations of the last frame (4 waves per 16x16 block; zeroed: no hint)
   if ((r = dalloc(c, (void **)&c->vol.rdur, grid16 * 4 * sizeof(unsigned)))) return fail(r);
   const size_t n = nvox(c);
@@ -1212,7 +1213,7 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
   // Z-slab contexts keep no bytes and never skip
   if (world == 1 && (r = dalloc(c, (void **)&c->vol.settled, c->vol.settled_bytes()))) return fail(r);
   if (world == 1 && (r = dalloc(c, (void **)&c->vol.sgate, 4))) return fail(r);
-  if ((r = dalloc(c, (void **)&c->skipcnt, 8))) return fail(r);
+  if ((r = dalloc(c, (void **)&c->skipcnt, 24))) return fail(r);
   {  // integrate dispatch order: identity until the first integrate has measured the intervals
     const size_t tiles = (size_t)c->vol.tiles_x * c->vol.tiles_y, items = tiles * integrate_chunks(c->vol);
     if ((r = dalloc(c, (void **)&c->vol.iwork, tiles * 4))) return fail(r);
@@ -1663,7 +1664,7 @@ int kfx_debug_count_settled(kfx_ctx *c, int on) {
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipStreamSynchronize(c->pstream));
     destroy_graphs(c);
-    HIPCHK(hipMemset(c->skipcnt, 0, 8));
+    HIPCHK(hipMemset(c->skipcnt, 0, 24));
   }
   c->vol.skipcnt = on ? c->skipcnt : nullptr;
   return KFX_OK;
@@ -1683,6 +1684,18 @@ int kfx_debug_get_settled(kfx_ctx *c, uint64_t out[2]) {
   unsigned long long n = 0;
   HIPCHK(hipMemcpy(&n, c->skipcnt, 8, hipMemcpyDeviceToHost));
   out[1] = n;
+  return KFX_OK;
+}
+
+int kfx_debug_get_hidden(kfx_ctx *c, uint64_t out[2]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out) return set_err(KFX_ERR_ARG, "null argument");
+  HIPCHK(hipStreamSynchronize(c->stream));  // the frames enqueued so far (their results stay pending)
+  unsigned long long n[3] = {0, 0, 0};
+  HIPCHK(hipMemcpy(n, c->skipcnt, 24, hipMemcpyDeviceToHost));
+  out[0] = n[1];
+  out[1] = n[2];
   return KFX_OK;
 }
 

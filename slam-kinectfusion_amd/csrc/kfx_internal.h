@@ -127,6 +127,7 @@ struct VolView {
   float trunc;
   float inv_trunc;  // RN(1/trunc), for the exact FMA division (kfx_kernels.hip div_rn)
   float far_k;      // far_clip_factor of the level-0 intrinsics (kfx_settled.h): integrate's far clips and certificate
+  float hid_k;      // hidden_clip_factor of the level-0 intrinsics (kfx_settled.h): integrate's hidden-brick certificate
   size_t slice;    // voxels per z slice (= X*Y)
   // Dilated occupancy of negative tsdf (raycast empty-space skipping, DESIGN.md
   // §4): bit set <=> some voxel within one brick of this brick may hold a
@@ -150,7 +151,9 @@ struct VolView {
   // large value): below 63 no voxel can hold weight 64, and integrate's waves
   // leave the settled bookkeeping out.  Allocated with `settled`.
   unsigned *sgate;
-  unsigned long long *skipcnt;  // kfx_debug_count_settled: bricks skipped by the last integrate (null: not counted)
+  // kfx_debug_count_settled: the last integrate's bricks skipped as settled [0], skipped as hidden [1] and,
+  // among the latter, those that hang over an end of their tile's interval [2] (null: not counted)
+  unsigned long long *skipcnt;
   // Integrate dispatch order (k_int_order): iwork[tile] = the length of the
   // tile's wave-uniform z interval in the last integrate, iperm[b] = the
   // (chunk * tiles + tile) item block b runs (longest estimated first; any

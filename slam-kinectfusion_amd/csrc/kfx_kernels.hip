@@ -1587,6 +1587,7 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   }
 #ifdef KFX_INT_TRACE
   const unsigned long long t_start = wall_clock64();
+  unsigned long long t_loop = 0ull;  // the z loop's entry
 #endif
   static_assert(KFX_INT_BLOCK == 64, "one wave per block: block b runs item iperm[b]");
   const int lane = threadIdx.x & 63;
@@ -1650,36 +1651,66 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   const int la = max(za, zl), lb = min(zb, zh);  // this lane's voxels of the chunk
   const bool live = lb >= la;
   if (__all(!live)) return;
-  // Settled bricks of this chunk that the frame cannot change (kfx_settled.h):
-  // lane k takes brick gbs + k when the chunk holds all of it; bit k of skipm.
+  // Bricks of this chunk that need no work in this frame (kfx_settled.h):
+  // hidden ones (behind every surface they project onto: no voxel can be
+  // updated) and settled ones the frame cannot change (§15).
+  // Both certificates read only the pose and the frame's depth grids, which no
+  // wave of this launch writes.  Lane k takes brick gbs + k; bit k of skipm
+  // when the chunk holds all of the brick.  The count-only instance never skips.
   // setm: the bytes now set among the bricks the chunk touches (bit k), kept
   // current by the loop so that it stores a byte only when the byte changes.
   // (A brick on a chunk boundary is never set inside a launch, so a stale 1
   // read there only repeats a neighbour's clear.)
   unsigned long long skipm = 0ull, setm = 0ull;
-  unsigned nskip = 0u;
   uint8_t *const sett = (!kCount && v.settled) ? v.settled + (size_t)tile * (v.bw * 64) - v.bz0 : nullptr;
-  if (sett) {
-    const int gb = (za >> 3) + lane;
+  if (!kCount) {
+    // (an opaque copy of the lane, as for the exchange after the loop: what the
+    // certificate derives from it must not stay live across the z loop)
+    int cl = lane;
+    asm volatile("" : "+v"(cl));
+    const int gb = (za >> 3) + cl;
     const bool inside = gb * 8 >= za && gb * 8 + 7 <= zb;
-    const bool isset = gb * 8 <= zb && sett[gb] != 0;
-    const bool set = inside && isset;
+    // (A hidden brick may also hang over the chunk's ends: none of its voxels
+    // needs work; below za only when the loop's first batch is the brick's
+    // first.  The code does not test where the chunk ends: int_chunk puts
+    // every inner boundary on a multiple of 8 slices, so only a tile's first
+    // and last chunk can hold part of a brick, and the rest of that brick
+    // lies outside the tile's interval.  With chunk cuts inside bricks two
+    // neighbouring waves would each step over their half, still correctly,
+    // since every voxel of the brick is hidden, and the debug count would
+    // count the brick twice.)
+    const bool touched = gb * 8 >= (za & ~(KFX_INT_KB - 1)) && gb * 8 <= zb;
+    const bool isset = sett && gb * 8 <= zb && sett[gb] != 0;
     setm = __ballot(isset);
-    if (__any(set)) {
-      // the pose again from LDS, into scalar registers (P kept live up to
-      // here in vector registers spills in the clip above)
-      asm volatile("" ::: "memory");
-      DevPose Q;
-      for (int i = 0; i < 9; ++i) Q.R[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_pose.R[i])));
-      for (int i = 0; i < 3; ++i) Q.t[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_pose.t[i])));
-      const bool cert = set && brick_certified(Q.R, Q.t, v.vs[0], v.vs[1], g.fx, g.fy, g.cx, g.cy, g.w, g.h, x & ~7,
-                                               y & ~7, gb * 8, v.trunc, dmin_grid(dl, g), (g.w + 15) >> 4, v.far_k);
-      skipm = __ballot(cert);
+    // the pose again from LDS, into scalar registers (P kept live up to
+    // here in vector registers spills in the clip above)
+    asm volatile("" ::: "memory");
+    DevPose Q;
+    for (int i = 0; i < 9; ++i) Q.R[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_pose.R[i])));
+    for (int i = 0; i < 3; ++i) Q.t[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_pose.t[i])));
+    const unsigned cert =
+        touched ? brick_certificates(Q.R, Q.t, v.vs[0], v.vs[1], g.fx, g.fy, g.cx, g.cy, g.w, g.h, (tile % v.tiles_x) * 8,
+                                    (tile / v.tiles_x) * 8, gb * 8, v.trunc, dmin_grid(dl, g), dmax_grid(dl, g),
+                                    isset && inside, (g.w + 15) >> 4, v.far_k, v.hid_k)
+               : 0u;
+    const unsigned long long freem = __ballot((cert & kBrickFree) != 0u);
+    skipm = freem | __ballot((cert & kBrickHidden) != 0u);
+    const unsigned long long overm = __ballot((cert & kBrickHidden) != 0u && !inside);
+    // debug counts, here rather than after the loop (nothing of them lives
+    // across it): the loop steps over every brick of skipm exactly once
+    if (v.skipcnt && skipm && cl == 0) {
+      const unsigned nf = (unsigned)__popcll(freem), nh = (unsigned)__popcll(skipm & ~freem);
+      if (nf) atomicAdd(v.skipcnt, (unsigned long long)nf);
+      if (nh) atomicAdd(v.skipcnt + 1, (unsigned long long)nh);
+      if (overm) atomicAdd(v.skipcnt + 2, (unsigned long long)__popcll(overm));
     }
   }
   // The bookkeeping runs where it can matter: a byte of the chunk is set, or
   // the volume has taken the 63 integrations since its last reset without
   // which no voxel holds weight 64 (VolView::sgate; an upload opens the gate).
+#ifdef KFX_INT_TRACE
+  t_loop = wall_clock64();
+#endif
   const bool track = sett && (setm != 0ull || __builtin_amdgcn_readfirstlane(*v.sgate) >= 63u);
 
   const float trunc = v.trunc;
@@ -1731,7 +1762,6 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
             for (int u = 0; u < 8; ++u) vc = add(vc, zs);  // (the loop's own adds: zs stays where the loop keeps it)
             iz += (Idx)8 * slice;
             z += 8;
-            ++nskip;
             continue;
           }
           zrun = zn - 1;  // (zn - z is a multiple of kB: the run ends with z == zn)
@@ -1932,7 +1962,6 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
     if (fastw) zloop(std::true_type{}, std::false_type{});
     else zloop(std::false_type{}, std::false_type{});
   }
-  if (!kCount && v.skipcnt && nskip && lane == 0) atomicAdd(v.skipcnt, (unsigned long long)nskip);  // debug count
   if (!kCount) {  // raycast skip maps
     // the exchange addresses are made here from an opaque copy of the lane:
     // shared with the prologue's shuffles they stay live across the z loop
@@ -1957,7 +1986,8 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
     r[1] = wall_clock64();
     r[2] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) |
            (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-    r[3] = (unsigned long long)tile | ((unsigned long long)chunk << 32);
+    // tile, chunk, the prologue's ticks (start to the z loop's entry, 20 bits)
+    r[3] = (unsigned long long)tile | ((unsigned long long)chunk << 32) | (min(t_loop - t_start, 0xfffffull) << 44);
   }
 #endif
   if (kCount) {
@@ -3369,7 +3399,7 @@ void launch_integrate(hipStream_t s, VolView v, LevelGeom g0, const float2 *dl0,
 #define KFX_LAUNCH_INT(C, I)                                                                             \
   hipLaunchKernelGGL((k_integrate<C, I>), grd, dim3(KFX_INT_BLOCK), 0, s, v, g0, dl0, dmap, invl, bgr, st, log, vpose, xpose, \
                      counters)
-  if (!counters && v.skipcnt) (void)hipMemsetAsync(v.skipcnt, 0, 8, s);  // debug: this launch's skipped bricks
+  if (!counters && v.skipcnt) (void)hipMemsetAsync(v.skipcnt, 0, 24, s);  // debug: this launch's skipped bricks
   if (counters) KFX_LAUNCH_INT(true, false);
   else if (idx32) KFX_LAUNCH_INT(false, true);
   else KFX_LAUNCH_INT(false, false);

@@ -39,7 +39,7 @@ EXPORTS = [
     "kfx_extract_mesh", "kfx_write_ply_mesh", "kfx_get_extract_ms", "kfx_set_extract_passes", "kfx_get_extract_passes", "kfx_set_slab_bound",
     "kfx_extract_points_attr", "kfx_extract_mesh_attr", "kfx_write_ply_attr", "kfx_write_ply_mesh_attr",
     "kfx_save_pointcloud_attr", "kfx_save_mesh_attr",
-    "kfx_debug_count_settled", "kfx_debug_get_settled",
+    "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
@@ -90,6 +90,7 @@ def lib():
         "kfx_debug_force_index64": ([vp, i], i),
         "kfx_debug_count_settled": ([vp, i], i),
         "kfx_debug_get_settled": ([vp, P(C.c_uint64)], i),
+        "kfx_debug_get_hidden": ([vp, P(C.c_uint64)], i),
         "kfx_debug_icp_band_ms": ([vp, i, i, i, P(C.c_float)], i),
         "kfx_debug_get_icp_sums": ([vp, P(C.c_int64)], i),
         "kfx_debug_cap_icp_blocks": ([vp, i, P(C.c_int32)], i),
@@ -506,6 +507,13 @@ class KinectFusion:
         """(bricks whose settled byte is set, bricks skipped by the last integrate)."""
         out = (C.c_uint64 * 2)()
         _check(lib().kfx_debug_get_settled(self._h, out), "kfx_debug_get_settled")
+        return int(out[0]), int(out[1])
+
+    def debug_get_hidden(self):
+        """(bricks the last integrate skipped as hidden, those among them that hang
+        over an end of their tile's interval); armed by debug_count_settled."""
+        out = (C.c_uint64 * 2)()
+        _check(lib().kfx_debug_get_hidden(self._h, out), "kfx_debug_get_hidden")
         return int(out[0]), int(out[1])
 
     def debug_get_icp_sums(self) -> np.ndarray:

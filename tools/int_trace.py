@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-wave timeline of k_integrate (debug library built with -DKFX_INT_TRACE):
 runs the C2 bench workload for a few frames, dumps the last integrate's wave
-records and prints the SIMD/CU occupancy over time and the wave-duration spread.
+records and prints the SIMD/CU occupancy over time, the wave-duration spread,
+and each wave's prologue time (start to the z loop's entry).
 usage: KFX_LIB_PATH=<trace lib> python3 tools/int_trace.py [out.npy|-] [frames]"""
 import ctypes as C
 import os
@@ -28,6 +29,9 @@ kf.synchronize()
 lib = kfx.lib()
 buf = (C.c_uint64 * (4 * 65536))()
 n = lib.kfx_debug_integrate_trace(buf, 65536)
+raw = np.frombuffer(buf, dtype=np.uint64)[: 4 * n].reshape(n, 4)
+raw = raw[raw[:, 1] > 0]
+pro = (raw[:, 3] >> np.uint64(44)).astype(np.int64) * 10  # ns
 a = np.frombuffer(buf, dtype=np.uint64)[: 4 * n].reshape(n, 4).astype(np.int64)
 launched = n
 a = a[a[:, 1] > 0]
@@ -57,12 +61,14 @@ for k in range(20):
     t = span * (k + 0.5) / 20
     print(f"  t={t / 1e3:6.1f} us resident {((st <= t) & (en > t)).sum() / 8192:5.2f}")
 print(f"wave-time / (span x 8192 slots) = {dur.sum() / (span * 8192):.3f}")
-chunk = a[:, 3] >> 32
+chunk = (a[:, 3] >> 32) & 0xff
+print(f"prologue us: med {np.median(pro) / 1e3:.2f} p90 {np.percentile(pro, 90) / 1e3:.2f} max {pro.max() / 1e3:.2f} "
+      f"sum / wave-time {pro.sum() / dur.sum():.3f}")
 for c in np.unique(chunk):
     m = chunk == c
     print(f"  chunk {c}: waves {m.sum():5d} start med {np.median(st[m]) / 1e3:6.1f} dur med {np.median(dur[m]) / 1e3:6.1f} "
           f"p90 {np.percentile(dur[m], 90) / 1e3:6.1f} max {dur[m].max() / 1e3:6.1f} us; ends after 90% of span: "
-          f"{(m & (en > 0.9 * span)).sum()}")
+          f"{(m & (en > 0.9 * span)).sum()}; prologue med {np.median(pro[m]) / 1e3:.2f} us")
 if len(sys.argv) > 1 and sys.argv[1] != "-":
     np.save(sys.argv[1], a)
 kf.close()
