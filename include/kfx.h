@@ -353,6 +353,31 @@ int kfx_set_extract_passes(kfx_ctx *ctx, int passes);
 #define KFX_RENDER_NORMAL 1
 int kfx_render(kfx_ctx *ctx, int type, uint8_t *out);
 
+/* Free-viewpoint render. */
+#define KFX_VIEW_PHONG 0   /* kfx_render's Phong, lit from the view camera's position */
+#define KFX_VIEW_NORMAL 1  /* kfx_render's normal colours */
+#define KFX_VIEW_COLOR 2   /* the fused colour, unshaded (below) */
+/* Render the volume as it stands from camera-to-world pose `cam_pose` (the pose
+ * record's convention) through `view` (any size, any fx fy cx cy).  out =
+ * width*height uchar3, pixels without a surface 0.  vmap / nmap (float3 AoS) and
+ * ts (float, metres along the ray, 0 = no hit) may each be NULL.
+ * The maps are the reference raycast's (tsdf_volume.cu:210-260) at `view` from
+ * cam2vol = volu_pose^-1 * cam_pose, level 0 only.  KFX_VIEW_COLOR blends the
+ * colours of the hit's 8 trilinear corners that lie in the volume and were ever
+ * coloured, with 8-bit fixed-point weights in integer arithmetic, in the input
+ * images' B, G, R order; a hit without such a corner keeps its Phong value.
+ * The call runs on the context's stream behind every queued frame and blocks
+ * until the image is on the host.  It writes nothing the tracker reads and
+ * leaves a pending tracking status to the next kfx_synchronize.
+ * KFX_ERR_ARG: a null view, cam_pose or out; a type outside 0..2; width or
+ * height below 1 or width*height above 2^26; a non-finite or zero fx or fy; a
+ * non-finite cx, cy or pose entry.  KFX_ERR_STATE: a slab context of a world
+ * larger than 1. */
+int kfx_render_view(kfx_ctx *ctx, const kfx_intrinsics *view, const kfx_pose *cam_pose,
+                    int type, uint8_t *out, float *vmap, float *nmap, float *ts);
+int kfx_get_view_ms(kfx_ctx *ctx, float *ms);   /* device ms of the last view (HIP events) */
+int kfx_write_ppm(const char *path, const uint8_t *bgr, int width, int height); /* binary P6, RGB */
+
 /* Order-free checksum of the (owned part of the) volume: out[0] = sum mod
  * 2^64 of a 64-bit mix of (x-fastest global voxel index, tsdf, weight,
  * colour) over every voxel, out[1] = voxels with weight > 0.  The sums of a

@@ -229,6 +229,13 @@ struct kfx_ctx {
   bool slab = false;
   int rank = 0, world = 1;
   uint8_t *render = nullptr;      // kfx_render output (allocated on first use)
+  // kfx_render_view: output pixels and [vmap | nmap | ts] planes (allocated on
+  // first use, grown for a larger view, freed in kfx_destroy), launch events
+  uint8_t *view_out = nullptr;
+  float *view_maps = nullptr;
+  size_t view_out_cap = 0, view_maps_cap = 0;
+  hipEvent_t ev_view[2]{};
+  float view_ms = 0.f;            // device time of the last view's launch
   uint8_t *mc_tab = nullptr;      // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded
@@ -1279,6 +1286,10 @@ int kfx_destroy(kfx_ctx *c) {
   if (c->cstream) (void)hipStreamDestroy(c->cstream);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   for (void *a : c->allocs) (void)hipFree(a);
+  if (c->view_out) (void)hipFree(c->view_out);
+  if (c->view_maps) (void)hipFree(c->view_maps);
+  for (hipEvent_t e : c->ev_view)
+    if (e) (void)hipEventDestroy(e);
   for (auto &e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {c->ev_prep, c->ev_free[0], c->ev_free[1], c->ev_icp, c->ev_group})
@@ -2233,6 +2244,121 @@ int kfx_render(kfx_ctx *c, int type, uint8_t *out) {
   HIPCHK(hipMemcpyAsync(out, c->render, 3 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return KFX_OK;
+}
+
+// ---- free-viewpoint render --------------------------------
+
+// Affine3f product and rigid inverse in the float order of the device's
+// pose_mul / pose_inv (k_ray_pose; the oracle's kfo_pose_mul / kfo_pose_inv):
+// this file is built without contraction, so the host sums round the same.
+static DevPose host_pose_mul(const DevPose &a, const DevPose &b) {
+  DevPose r;
+  for (int j = 0; j < 3; ++j) {
+    for (int i = 0; i < 3; ++i) {
+      float v = 0.f;
+      for (int k = 0; k < 3; ++k) v += a.R[3 * j + k] * b.R[3 * k + i];
+      r.R[3 * j + i] = v;
+    }
+    float d = 0.f;
+    for (int k = 0; k < 3; ++k) d += a.R[3 * j + k] * b.t[k];
+    r.t[j] = d + a.t[j];
+  }
+  return r;
+}
+static DevPose host_pose_inv(const DevPose &a) {
+  DevPose r;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) r.R[3 * i + j] = a.R[3 * j + i];
+  for (int j = 0; j < 3; ++j) {
+    float d = 0.f;
+    for (int k = 0; k < 3; ++k) d += a.R[3 * k + j] * a.t[k];
+    r.t[j] = -d;
+  }
+  return r;
+}
+
+// (re)allocate one of the view's buffers for at least `bytes` (grown, never
+// shrunk; the previous view has completed: every view call ends with a sync)
+static int view_reserve(void **p, size_t *cap, size_t bytes) {
+  if (*cap >= bytes) return KFX_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) {
+    *p = nullptr;
+    return set_err(KFX_ERR_OOM, "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
+  }
+  *cap = bytes;
+  return KFX_OK;
+}
+
+int kfx_render_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_pose, int type, uint8_t *out,
+                    float *vmap, float *nmap, float *ts) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!view || !cam_pose || !out) return set_err(KFX_ERR_ARG, "null argument");
+  if (type < KFX_VIEW_PHONG || type > KFX_VIEW_COLOR) return set_err(KFX_ERR_ARG, "view type outside 0..2");
+  if (view->width < 1 || view->height < 1 || (int64_t)view->width * view->height > ((int64_t)1 << 26))
+    return set_err(KFX_ERR_ARG, "view size: width, height >= 1 and width * height <= 2^26");
+  if (!std::isfinite(view->fx) || !std::isfinite(view->fy) || view->fx == 0.f || view->fy == 0.f ||
+      !std::isfinite(view->cx) || !std::isfinite(view->cy))
+    return set_err(KFX_ERR_ARG, "view intrinsics: finite, fx and fy non-zero");
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? cam_pose->R[i] : cam_pose->t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite view pose");
+  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "render_view on one slab of several");
+  const size_t np = (size_t)view->width * view->height;
+  const bool maps = vmap || nmap || ts;
+  if ((r = view_reserve((void **)&c->view_out, &c->view_out_cap, 3 * np))) return r;
+  if (maps && (r = view_reserve((void **)&c->view_maps, &c->view_maps_cap, 28 * np))) return r;
+  for (hipEvent_t &e : c->ev_view)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  float *dv = vmap ? c->view_maps : nullptr, *dn = nmap ? c->view_maps + 3 * np : nullptr,
+        *dt = ts ? c->view_maps + 6 * np : nullptr;
+  const DevPose cam = to_dev(*cam_pose);
+  const DevPose c2v = host_pose_mul(host_pose_inv(to_dev(c->p.volu_pose)), cam);  // tsdf_volume.cpp:59
+  const LevelGeom g = {view->width, view->height, view->fx, view->fy, view->cx, view->cy};
+  // on the frame stream, behind every queued frame's integrate; nothing the
+  // tracker reads is written, and the pending tracking status is left alone
+  HIPCHK(hipEventRecord(c->ev_view[0], c->stream));
+  launch_view(c->stream, c->vol, g, c2v, cam.t, type, c->view_out, dv, dn, dt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_view[1], c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->view_out, 3 * np, hipMemcpyDeviceToHost, c->stream));
+  if (vmap) HIPCHK(hipMemcpyAsync(vmap, dv, 12 * np, hipMemcpyDeviceToHost, c->stream));
+  if (nmap) HIPCHK(hipMemcpyAsync(nmap, dn, 12 * np, hipMemcpyDeviceToHost, c->stream));
+  if (ts) HIPCHK(hipMemcpyAsync(ts, dt, 4 * np, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->view_ms, c->ev_view[0], c->ev_view[1]));
+  return KFX_OK;
+}
+
+int kfx_get_view_ms(kfx_ctx *c, float *ms) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!ms) return set_err(KFX_ERR_ARG, "null ms");
+  *ms = c->view_ms;
+  return KFX_OK;
+}
+
+int kfx_write_ppm(const char *path, const uint8_t *bgr, int width, int height) {
+  if (!path || !bgr || width < 1 || height < 1) return set_err(KFX_ERR_ARG, "bad argument");
+  FILE *f = std::fopen(path, "wb");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  std::fprintf(f, "P6\n%d %d\n255\n", width, height);
+  std::vector<uint8_t> row(3 * (size_t)width);
+  bool ok = true;
+  for (int y = 0; y < height && ok; ++y) {
+    const uint8_t *s = bgr + 3 * (size_t)y * width;
+    for (int x = 0; x < width; ++x) {
+      row[3 * x] = s[3 * x + 2];
+      row[3 * x + 1] = s[3 * x + 1];
+      row[3 * x + 2] = s[3 * x];
+    }
+    ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? KFX_OK : set_err(KFX_ERR_ARG, std::string("write failed: ") + path);
 }
 
 // ---- point cloud / PLY -----------------------------------------------------

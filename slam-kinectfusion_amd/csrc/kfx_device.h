@@ -1,5 +1,6 @@
 // kfx_device.h — device code that two or more of the kernel files
-// (kfx_kernels.hip, kfx_extract.hip, kfx_volume_io.hip) use.  Everything lives
+// (kfx_kernels.hip, kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip) use
+// (the raycast march's functions: kfx_ray.h).  Everything lives
 // in an unnamed namespace: each file gets its own internal copy.  A helper with
 // one user lives in that file instead.
 #pragma once
@@ -36,6 +37,14 @@ __device__ __forceinline__ void st3(float *p, size_t i, f3 v) {
   p[3 * i] = v.x;
   p[3 * i + 1] = v.y;
   p[3 * i + 2] = v.z;
+}
+
+// The uchar conversion and __m_normalize of the shaders (k_render, k_view):
+// IEEE sqrt and division, NaN -> 0, as the oracle's kfo_render.
+__device__ __forceinline__ uint8_t render_u8(float x) { return x >= 1.f ? (uint8_t)fminf(x, 255.f) : 0; }
+__device__ __forceinline__ f3 normalized_ieee(f3 v) {
+  const float t = sqrtf(dot(v, v));
+  return {v.x / t, v.y / t, v.z / t};
 }
 
 // z is the global slice; the view stores slices [zb, zb+zn) (tile-column

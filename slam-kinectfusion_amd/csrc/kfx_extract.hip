@@ -447,12 +447,8 @@ __global__ void k_scan_add(unsigned long long *out, const unsigned long long *bs
 // previous frame's level-0 maps, lit from the last pose's camera position
 // (kinectfusion.cpp:33-47).  D as in the oracle (kfo_render): IEEE sqrt and
 // division in __m_normalize, pow(h, 10) as h8 * h2, NaN → 0 in the uchar
-// conversion; `0.5*light_coffi` stays double as in the source.
-__device__ __forceinline__ uint8_t render_u8(float x) { return x >= 1.f ? (uint8_t)fminf(x, 255.f) : 0; }
-__device__ __forceinline__ f3 normalized_ieee(f3 v) {
-  const float t = sqrtf(dot(v, v));
-  return {v.x / t, v.y / t, v.z / t};
-}
+// conversion (render_u8, normalized_ieee: kfx_device.h); `0.5*light_coffi`
+// stays double as in the source.
 __global__ __launch_bounds__(256) void k_render(const float *__restrict__ vmap, const float *__restrict__ nmap,
                                                 int n, const DevState *st, const DevPose *log, int type,
                                                 uint8_t *__restrict__ out) {

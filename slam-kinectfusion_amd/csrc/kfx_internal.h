@@ -1,5 +1,5 @@
 // kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip,
-// kfx_extract.hip, kfx_volume_io.hip) and the host runtime (kfx_api.hip).  Not part of the public ABI.
+// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip) and the host runtime (kfx_api.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -363,6 +363,14 @@ void launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offs
 // renderPhong (type 0) / renderNormals (type 1) of the level-0 maps into w*h uchar3
 void launch_render(hipStream_t s, const float *vmap, const float *nmap, int n, const DevState *st,
                    const DevPose *log, int type, uint8_t *out);
+
+// ---- kfx_view.hip ---------------------------------------------------------
+// free-viewpoint render: the reference raycast of the volume
+// at intrinsics g from cam2vol, shaded (type: KFX_VIEW_*; eye = the camera
+// position the Phong shader lights from) into out = w*h uchar3 in one launch;
+// vmap / nmap (float3) and ts (Ts of the hit, 0: none) are stored when non-null
+void launch_view(hipStream_t s, VolView v, LevelGeom g, DevPose cam2vol, const float eye[3], int type, uint8_t *out,
+                 float *vmap, float *nmap, float *ts);
 
 // ---- kfx_volume_io.hip ----------------------------------------------------
 void launch_export_records(hipStream_t s, VolView v, int z0, int nz, uint64_t *dst);

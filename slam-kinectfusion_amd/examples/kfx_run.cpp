@@ -2,8 +2,9 @@
 // directory, over the C-ABI only (no OpenCV, no viz): depth_sensor::open /
 // getFrame → kinectfusion::pipeline per frame → poses.txt (and optionally the
 // point cloud PLY, main.cpp:43-44; the coloured, oriented cloud and mesh are
-// extensions: kfx_save_pointcloud_attr / kfx_save_mesh_attr).
-//   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply]
+// extensions: kfx_save_pointcloud_attr / kfx_save_mesh_attr; view.ppm is the
+// fused colour rendered from the last tracked pose, kfx_render_view).
+//   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
 #include <chrono>
 #include <cstdio>
 #include <vector>
@@ -12,7 +13,8 @@
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply]\n",
+    std::fprintf(stderr,
+                 "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]\n",
                  argv[0]);
     return 2;
   }
@@ -66,6 +68,16 @@ int main(int argc, char **argv) {
       (argc > 5 && kfx_save_mesh_attr(ctx, argv[5], 0) != KFX_OK)) {
     std::fprintf(stderr, "error: %s\n", kfx_last_error());
     return 1;
+  }
+  if (argc > 6) {  // the fused colour seen from the last tracked pose, at the dataset's intrinsics
+    kfx_pose last;
+    std::vector<uint8_t> img((size_t)intr.width * intr.height * 3);
+    if (kfx_get_cur_camera_pose(ctx, &last) != KFX_OK ||
+        kfx_render_view(ctx, &intr, &last, KFX_VIEW_COLOR, img.data(), nullptr, nullptr, nullptr) != KFX_OK ||
+        kfx_write_ppm(argv[6], img.data(), intr.width, intr.height) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
   }
   std::printf("end! %d frames, frame_count %d, %.3f ms/frame in kfx_pipeline (host frames, PCIe incl.)\n", n,
               frames, n ? 1e3 * gpu_s / n : 0.0);

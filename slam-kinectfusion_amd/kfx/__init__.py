@@ -20,7 +20,7 @@ from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, Intr
 
 __all__ = ["KinectFusion", "KfxError", "Dataset", "png_info", "png_read_bgr8", "png_read_depth", "parse_intr",
            "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "write_ply_attr", "write_ply_mesh_attr",
-           "VERTEX_DTYPE", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
+           "write_ppm", "VIEW_KINDS", "VERTEX_DTYPE", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
            "default_params", "KFX_FRAME_CUR", "KFX_FRAME_PREV", "KFX_OK", "KFX_TRACKING_LOST", "EXPORTS"]
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,6 +39,7 @@ EXPORTS = [
     "kfx_extract_mesh", "kfx_write_ply_mesh", "kfx_get_extract_ms", "kfx_set_extract_passes", "kfx_get_extract_passes", "kfx_set_slab_bound",
     "kfx_extract_points_attr", "kfx_extract_mesh_attr", "kfx_write_ply_attr", "kfx_write_ply_mesh_attr",
     "kfx_save_pointcloud_attr", "kfx_save_mesh_attr",
+    "kfx_render_view", "kfx_get_view_ms", "kfx_write_ppm",
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
@@ -138,6 +139,9 @@ def lib():
         "kfx_slab_frame_finish": ([vp, P(C.c_uint32)], i),
         "kfx_extract_points": ([vp, P(f), C.c_int64, P(C.c_int64)], i),
         "kfx_render": ([vp, i, P(C.c_uint8)], i),
+        "kfx_render_view": ([vp, P(Intrinsics), P(Pose), i, P(C.c_uint8), P(f), P(f), P(f)], i),
+        "kfx_get_view_ms": ([vp, P(f)], i),
+        "kfx_write_ppm": ([C.c_char_p, P(C.c_uint8), i, i], i),
         "kfx_volume_checksum": ([vp, P(C.c_uint64)], i),
         "kfx_write_ply": ([C.c_char_p, P(f), C.c_int64], i),
         "kfx_save_pointcloud": ([vp, C.c_char_p, C.c_int64], i),
@@ -207,6 +211,17 @@ def write_ply(path: str, xyz: np.ndarray):
     """kinectfusion::savePointcloud's ASCII PLY for an (N, 3) float32 array."""
     xyz = np.ascontiguousarray(xyz, np.float32)
     _check(lib().kfx_write_ply(path.encode(), fptr(xyz), xyz.shape[0]), "kfx_write_ply")
+
+
+VIEW_KINDS = {"phong": 0, "normal": 1, "color": 2}  # KFX_VIEW_*
+
+
+def write_ppm(path: str, bgr: np.ndarray):
+    """Binary PPM (P6, RGB) of an (H, W, 3) uint8 image in the ABI's BGR order."""
+    img = np.ascontiguousarray(bgr, np.uint8)
+    assert img.ndim == 3 and img.shape[2] == 3
+    _check(lib().kfx_write_ppm(path.encode(), img.ctypes.data_as(C.POINTER(C.c_uint8)), img.shape[1], img.shape[0]),
+           "kfx_write_ppm")
 
 
 # kfx_vertex (include/kfx.h): position, unit normal, colour in the ABI's BGR order + a (255: coloured)
@@ -593,6 +608,31 @@ class KinectFusion:
         _check(lib().kfx_render(self._h, 0 if kind == "phong" else 1, out.ctypes.data_as(C.POINTER(C.c_uint8))),
                "kfx_render")
         return out
+
+    def render_view(self, intr, pose, kind: str = "phong", maps: bool = False):
+        """kfx_render_view: the volume as it stands seen from camera-to-world
+        `pose` (4x4 matrix or Pose) through `intr` (any size and focal lengths);
+        kind "phong", "normal" or "color" (the fused colour, BGR).  Returns the
+        (H, W, 3) uint8 image, with maps=True (image, vmap, nmap, ts): the
+        view's (H, W, 3) float32 vertex and normal maps and the (H, W) float32
+        distance along each ray (0: no surface).  Tracking state is untouched."""
+        I = Intrinsics.from_any(intr)
+        P = pose if isinstance(pose, Pose) else Pose.from_matrix(pose)
+        h, w = max(I.height, 0), max(I.width, 0)
+        out = np.zeros((h, w, 3), np.uint8)
+        vm = np.zeros((h, w, 3), np.float32) if maps else None
+        nm = np.zeros((h, w, 3), np.float32) if maps else None
+        ts = np.zeros((h, w), np.float32) if maps else None
+        _check(lib().kfx_render_view(self._h, C.byref(I), C.byref(P), VIEW_KINDS[kind],
+                                     out.ctypes.data_as(C.POINTER(C.c_uint8)), fptr(vm) if maps else None,
+                                     fptr(nm) if maps else None, fptr(ts) if maps else None), "kfx_render_view")
+        return (out, vm, nm, ts) if maps else out
+
+    def view_ms(self) -> float:
+        """Device milliseconds of the last render_view launch (HIP events)."""
+        ms = C.c_float()
+        _check(lib().kfx_get_view_ms(self._h, C.byref(ms)), "kfx_get_view_ms")
+        return float(ms.value)
 
     def extract_mesh(self, cap: int = 50_000_000) -> np.ndarray:
         """Marching-cubes triangles, (N, 3, 3) float32 world coordinates (canonical order)."""
