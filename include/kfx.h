@@ -194,6 +194,16 @@ int kfx_debug_get_settled(kfx_ctx *ctx, uint64_t out[2]);
  * they project onto, out[1] = those among them that hang over an end of their
  * tile's interval (both 0 while the count is off). */
 int kfx_debug_get_hidden(kfx_ctx *ctx, uint64_t out[2]);
+/* Debug switch of integrate's per-frame tile kernel (added
+ * under ABI version 2, nothing else changed).  On (the default where the
+ * context keeps a tile table: a whole volume, not 1024..2047 slices deep, with
+ * more than one z-chunk per column tile) a small kernel in front of the
+ * integrate launch prepares what the integrate waves need once per tile; on == 0 makes every
+ * wave compute it for itself again, as contexts without a table always do.
+ * Captured graphs are dropped on a change.  Returns 1 if the tile kernel is in
+ * use after the call, 0 if not, <0 on error.  Results are identical either
+ * way. */
+int kfx_debug_int_tiles(kfx_ctx *ctx, int on);
 /* Debug hooks of the ICP reduction (added under ABI version 2,
  * nothing else changed).  kfx_debug_get_icp_sums: the 27 int64 fixed-point
  * sums (kfx_stage_icp_accumulate's layout) of the last ICP iteration that ran

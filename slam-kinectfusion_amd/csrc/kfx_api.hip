@@ -163,6 +163,7 @@ struct kfx_ctx {
   FrameView curb[2]{};
   float2 *dl0b[2]{};
   unsigned long long *skipcnt = nullptr;  // VolView::skipcnt's three words (kfx_debug_count_settled)
+  char *itab = nullptr;  // VolView::itab's allocation (kfx_debug_int_tiles switches the view's pointer)
   IcpPlan planb[2]{};
   int par = 0;
   bool overlap = true;
@@ -1228,6 +1229,12 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
     std::vector<unsigned> iota(items);
     for (size_t i = 0; i < items; ++i) iota[i] = (unsigned)i;
     HIPCHK(hipMemcpy(c->vol.iperm, iota.data(), items * 4, hipMemcpyHostToDevice));
+    // integrate's tile table (k_int_tiles), where launch_integrate uses one:
+    // a whole volume in geometric chunks, more than one per tile
+    if (world == 1 && integrate_tiles(c->vol)) {
+      if ((r = dalloc(c, (void **)&c->itab, VolView::itab_bytes(tiles, (size_t)integrate_chunks(c->vol))))) return fail(r);
+      c->vol.itab = c->itab;
+    }
   }
   {
     // the raycast start signal needs hipStreamWaitValue32; it
@@ -1666,6 +1673,19 @@ int kfx_debug_force_index64(kfx_ctx *c, int on) {
   }
   c->vol.force64 = on != 0;
   return KFX_OK;
+}
+
+int kfx_debug_int_tiles(kfx_ctx *c, int on) {
+  int r = check_ctx(c);
+  if (r) return r;
+  char *const want = on ? c->itab : nullptr;
+  if (c->vol.itab != want) {  // captured frames hold the other kernels
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->pstream));
+    destroy_graphs(c);
+  }
+  c->vol.itab = want;
+  return c->vol.itab ? 1 : 0;
 }
 
 int kfx_debug_count_settled(kfx_ctx *c, int on) {

@@ -114,6 +114,17 @@ struct IcpSync {
 // copy) so that raycast never needs a halo exchange.  A single-GPU volume is
 // the slab zb = own0 = 0, zn = own1 = Z.  X, Y, Z are always the global dims.
 constexpr int kSlabHalo = 4;
+// One (tile, chunk) item of integrate's tile table (VolView::itab): all
+// wave-uniform, one 64-B line.  zb < za: the item has no work.
+struct IntTileHdr {
+  int za, zb;                       // the chunk's slices
+  unsigned long long skipm, setm;   // bricks (za >> 3) + k to step over / whose settled byte is set
+  int kind;                         // frame kind (2: reset)
+  int fast;                         // column_fast of every live lane at the chunk's start
+  float zs[3];                      // vc's step per slice
+  int pad[5];
+};
+static_assert(sizeof(IntTileHdr) == 64, "one line per item");
 struct VolView {
   int16_t *tsdf;
   uint8_t *weight;  // D: u8 storage of the reference's int16 weight (values 0..MAX_WEIGHT; 0..255 accepted on upload)
@@ -164,6 +175,18 @@ struct VolView {
   int iadapt;  // length-capped chunks + longest-first order (deep volumes), else geometric chunks
   int force64;  // kfx_debug_force_index64: integrate / raycast take the 64-bit-index kernels at any size
   unsigned *rdur;  // raycast: each wave's duration in the last frame (1024-cycle units; issue priority hint)
+  // Integrate's per-frame tile table (k_int_tiles): what a
+  // (tile, chunk) wave's prologue used to compute, written once per tile
+  // directly before k_integrate.  Null: the waves compute it themselves
+  // (count-only pass, Z-slabs, length-capped chunks, one chunk per tile).
+  //   [tiles][64] int2 {zl, zh} | [tiles][nchunk] IntTileHdr | [tiles][nchunk][3][64] float vc
+  char *itab;
+  __host__ __device__ static size_t itab_bytes(size_t tiles, size_t nchunk) { return tiles * (512 + nchunk * (64 + 768)); }
+  __host__ __device__ int2 *itab_zlh() const { return (int2 *)itab; }
+  __host__ __device__ struct IntTileHdr *itab_hdr() const { return (struct IntTileHdr *)(itab + (size_t)tiles_x * tiles_y * 512); }
+  __host__ __device__ float *itab_vc() const {
+    return (float *)(itab + (size_t)tiles_x * tiles_y * (512 + (size_t)inchunk * 64));
+  }
   __host__ __device__ size_t bocc_bytes() const { return (size_t)tiles_x * tiles_y * bw * 8; }
   __host__ __device__ size_t socc_bytes() const { return (size_t)stx * sty * sw * 4; }
   __host__ __device__ size_t settled_bytes() const { return (size_t)tiles_x * tiles_y * bw * 64; }
@@ -331,6 +354,8 @@ void launch_host_fetch(hipStream_t s, const void *src0, void *dst0, size_t n0, c
                        size_t n1);
 // z-chunks per column tile of k_integrate (the iperm item count is tiles x this)
 int integrate_chunks(const VolView &v);
+// integrate reads its waves' prologue from a tile table (VolView::itab, k_int_tiles) on this volume
+bool integrate_tiles(const VolView &v);
 // per global slice: voxels passing integrate's depth test at vol2cam (an estimate, slab balancing)
 void launch_slice_work(hipStream_t s, const VolView &v, DevPose vol2cam, LevelGeom g0, const float2 *dl0,
                        unsigned long long *hist);

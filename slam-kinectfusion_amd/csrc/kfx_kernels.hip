@@ -19,6 +19,7 @@
 #include "kfx_raystep.h"
 #include "kfx_settled.h"
 #include "kfx_sqrtbound.h"
+#include "kfx_tilemask.h"
 
 namespace kfx {
 namespace {
@@ -1193,6 +1194,13 @@ __device__ void frame_bookkeeping(DevState *st, DevPose *log, int kind, const De
 // alternating pairs, 2 and 5 slower or neutral: profiles/r06_int_chunks_ab.txt)
 #define KFX_INT_WAVES 16384
 #endif
+#ifndef KFX_INT_WAVES_TAB
+// the same where the waves take their prologue from the tile table (k_int_tiles,
+// DESIGN.md §19): an item's start is cheap there, so shorter items pay (C2: 6
+// chunks; frame 0.3296-0.3321 ms at 4 chunks, 0.3221-0.3240 at 6, 0.3227-0.3241
+// at 8, five alternating rounds: profiles/int_tiles_ab.txt)
+#define KFX_INT_WAVES_TAB 24576
+#endif
 
 // Solve alpha + beta*z >= 0 into [lo, hi] (float, approximate quotient: the
 // callers widen the result by 2 slices, far above the float error; a NaN
@@ -1487,7 +1495,9 @@ constexpr RcpTable make_rcp_table() {
 }
 __constant__ RcpTable c_rtab = make_rcp_table();
 
-template <bool kCount, bool kIdx32>
+// kTab: the prologue comes from the tile table (VolView::itab, written by
+// k_int_tiles directly before this launch): one round of loads, then the loop.
+template <bool kCount, bool kIdx32, bool kTab = false>
 __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(KFX_INT_OCC, KFX_INT_OCC))) void k_integrate(VolView v, LevelGeom g,
                                                    const float2 *__restrict__ dl,
                                                    const float *__restrict__ dmap,
@@ -1501,8 +1511,9 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   __shared__ float rtab[257];
   __shared__ DevPose s_pose;
   __shared__ int s_kind;
+  static_assert(!(kTab && kCount), "the count-only pass keeps the in-wave prologue");
   for (int i = threadIdx.x; i < 257; i += KFX_INT_BLOCK) rtab[i] = c_rtab.v[i];
-  if (threadIdx.x == 0) {  // (inline rather than int_frame_pose: that form spills in the loop)
+  if (threadIdx.x == 0 && (!kTab || blockIdx.x == 0)) {  // (inline rather than int_frame_pose: that form spills in the loop)
     if (xpose) {  // stage seam: explicit vol2cam
       s_kind = 1;
       for (int i = 0; i < 9; ++i) s_pose.R[i] = xpose[i];
@@ -1545,7 +1556,9 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   const int x = (tile % v.tiles_x) * 8 + (lane & 7);
   const int y = (tile / v.tiles_x) * 8 + (lane >> 3);
   const size_t base = (size_t)tile * v.tile_voxels() + lane;  // this column's (x, y, zb)
-  if (s_kind == 2) {  // reset(): whole volume zeroed (A5 D)
+  const IntTileHdr *const hdr = kTab ? v.itab_hdr() + ((size_t)tile * nchunk + chunk) : nullptr;  // (wave-uniform)
+  const int kind = kTab ? hdr->kind : s_kind;
+  if (kind == 2) {  // reset(): whole volume zeroed (A5 D)
     if (kCount) return;
     const int z0 = (int)((long long)v.zn * chunk / nchunk);
     const int z1 = (int)((long long)v.zn * (chunk + 1) / nchunk);
@@ -1566,9 +1579,31 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
     }
     return;
   }
-  const DevPose P = s_pose;
   f3 vc, zs;
   int zl, zh, za, zb, z;
+  unsigned long long skipm = 0ull, setm = 0ull;
+  uint8_t *const sett = (!kCount && v.settled) ? v.settled + (size_t)tile * (v.bw * 64) - v.bz0 : nullptr;
+  bool live = true, tab_fast = false;
+  int la, lb;
+  if constexpr (kTab) {
+    // everything below up to the loop, from the table (k_int_tiles ran the
+    // same device functions once for the tile)
+    za = hdr->za;
+    zb = hdr->zb;
+    if (zb < za) return;  // no interval, an emptied chunk or no live lane
+    skipm = hdr->skipm;
+    setm = hdr->setm;
+    tab_fast = hdr->fast != 0;
+    zs = {hdr->zs[0], hdr->zs[1], hdr->zs[2]};
+    const int2 own = v.itab_zlh()[(size_t)tile * 64 + lane];
+    zl = own.x, zh = own.y;
+    const float *const row = v.itab_vc() + ((size_t)tile * nchunk + chunk) * 192 + lane;
+    vc = {row[0], row[64], row[128]};
+    z = za & ~(KFX_INT_KB - 1);
+    la = max(za, zl), lb = min(zb, zh);
+    (void)x, (void)y;
+  } else {
+  const DevPose P = s_pose;
   int_column(v, g, dl, P, x, y, vc, zs, zl, zh);
   // The wave takes a chunk of the UNION of its lanes' intervals, so all 64
   // lanes step the same z and each voxel load / store of the wave is one
@@ -1595,8 +1630,8 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   // chunk of a far slab replays its column from z = 0)
   z = za & ~(KFX_INT_KB - 1);
   vc = replay(vc, zs, 0, z, v.zb > 0 ? KFX_FF_MIN_SLAB : KFX_FF_MIN);
-  const int la = max(za, zl), lb = min(zb, zh);  // this lane's voxels of the chunk
-  const bool live = lb >= la;
+  la = max(za, zl), lb = min(zb, zh);  // this lane's voxels of the chunk
+  live = lb >= la;
   if (__all(!live)) return;
   // Bricks of this chunk that need no work in this frame (kfx_settled.h):
   // hidden ones (behind every surface they project onto: no voxel can be
@@ -1608,8 +1643,6 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   // current by the loop so that it stores a byte only when the byte changes.
   // (A brick on a chunk boundary is never set inside a launch, so a stale 1
   // read there only repeats a neighbour's clear.)
-  unsigned long long skipm = 0ull, setm = 0ull;
-  uint8_t *const sett = (!kCount && v.settled) ? v.settled + (size_t)tile * (v.bw * 64) - v.bz0 : nullptr;
   if (!kCount) {
     // (an opaque copy of the lane, as for the exchange after the loop: what the
     // certificate derives from it must not stay live across the z loop)
@@ -1652,6 +1685,7 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
       if (overm) atomicAdd(v.skipcnt + 2, (unsigned long long)__popcll(overm));
     }
   }
+  }
   // The bookkeeping runs where it can matter: a byte of the chunk is set, or
   // the volume has taken the 63 integrations since its last reset without
   // which no voxel holds weight 64 (VolView::sgate; an upload opens the gate).
@@ -1678,8 +1712,8 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
   constexpr Idx slice = 64;  // index step per z (tile-column layout)
   Idx iz = (Idx)base + (Idx)(z - v.zb) * slice;  // voxel index of (x, y, z) (below the store for z < zb: never used)
   static_assert(KFX_INT_KB == 4, "two batches per brick");
+  const bool fastw = kTab ? tab_fast : __all(!live || column_fast(vc, zs, v.Z));  // wave-uniform
   bool sgood = false;  // this lane's voxels of the current brick so far: all updated with ts = 1, nothing changed
-  const bool fastw = __all(!live || column_fast(vc, zs, v.Z));  // wave-uniform
   const float fw = (float)g.w, fh = (float)g.h;
   // Batches of kB voxels: positions, projections, the kB {depth, 1/lambda}
   // gathers, then the kB tsdf/weight loads are issued back to back
@@ -1944,6 +1978,152 @@ __global__ __launch_bounds__(KFX_INT_BLOCK) __attribute__((amdgpu_waves_per_eu(K
     atomicAdd(&counters[32 + sh], (unsigned long long)cv);
     atomicAdd(&counters[48 + sh], (unsigned long long)cg);
     if (lane == 0) atomicAdd(&counters[64 + sh], (unsigned long long)cb);  // per-wave count (wave-uniform)
+  }
+}
+
+// The tile table of k_integrate<.., kTab> (VolView::itab): a
+// block of two waves per column tile runs, once, what each of the tile's chunk
+// waves otherwise computes for itself — the same device functions on the same
+// inputs, so every table entry holds the bits the wave would have made.
+// Both waves:
+//   * the frame kind and vol2cam pose, resolved as k_integrate's preamble does
+//     (wave-uniform loads, issued together);
+//   * int_column, the union, int_tile_clip: lanes' [zl, zh];
+//   * int_chunk for every chunk (lane c computes chunk c).
+// Wave 0, the sweep: one pass of vc from slice 0 through every chunk's first
+// batch slice (replay per leg: the reference's adds, or their exact
+// fast-forward), vc stored there per lane, and column_fast at that point.
+// Wave 1, the masks: the iwork store, the settled bytes and
+// brick_certificates once per brick of the interval, lane k <-> brick
+// (wl >> 3) + k in rounds of 64, turned into each chunk's skipm / setm by
+// chunk_masks_round (kfx_tilemask.h; lane c keeps chunk c's masks), and the
+// debug skip counts, once.  (Two waves because the sweep is bound by the
+// vector unit and the masks by memory round trips: in one wave the phases of
+// all resident waves coincide and the kernel takes their sum.)
+// An item without work (no interval, a chunk emptied by the brick rounding,
+// no live lane) gets zb < za.  Launched directly before k_integrate on its
+// stream; writes only the table (and iwork).
+__global__ __launch_bounds__(128) void k_int_tiles(VolView v, LevelGeom g, const float2 *__restrict__ dl,
+                                                   const DevState *__restrict__ st, DevPose vpose, const float *xpose) {
+  const int lane = threadIdx.x & 63, tile = blockIdx.x, nchunk = v.inchunk;
+  const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  int kind = 1;
+  DevPose P;
+  if (xpose) {  // stage seam: explicit vol2cam
+    for (int i = 0; i < 9; ++i) P.R[i] = xpose[i];
+    for (int i = 0; i < 3; ++i) P.t[i] = xpose[9 + i];
+  } else {
+    // (everything the choice below can need, loaded before the first use)
+    const int mode = st->mode, fail = st->icp_fail;
+    const unsigned tag = st->int_tag, serial = st->frame_serial;
+    const DevPose tagged = st->int_v2c;
+    kind = mode == MODE_BOOT ? 0 : (fail ? 2 : 1);  // frame_kind
+    if (kind == 1 && tag == serial) {
+      P = tagged;
+    } else if (kind != 2) {
+      P = pose_mul(pose_inv(frame_pose(st, nullptr, kind)), vpose);  // tsdf_volume.cpp:50
+    } else {
+      P = pose_identity();  // (unused)
+    }
+  }
+  IntTileHdr *const hdr = v.itab_hdr() + (size_t)tile * nchunk;
+  // the masks' wave writes every field of an item's header but `fast`, which the sweep knows
+  auto put = [&](int c, int za, int zb, unsigned long long skipm, unsigned long long setm, f3 zs) {
+    IntTileHdr *const h = hdr + c;
+    h->za = za, h->zb = zb;
+    h->skipm = skipm, h->setm = setm;
+    h->kind = kind;
+    h->zs[0] = zs.x, h->zs[1] = zs.y, h->zs[2] = zs.z;
+  };
+  if (kind == 2) {  // reset: the waves need only the kind
+    if (role == 1 && lane < nchunk) put(lane, 0, -1, 0ull, 0ull, f3{0.f, 0.f, 0.f});
+    return;
+  }
+  const int x = (tile % v.tiles_x) * 8 + (lane & 7);
+  const int y = (tile / v.tiles_x) * 8 + (lane >> 3);
+  f3 vc, zs;
+  int zl, zh;
+  int_column(v, g, dl, P, x, y, vc, zs, zl, zh);
+  int wl = zl, wh = zh;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    wl = min(wl, __shfl_xor(wl, off));
+    wh = max(wh, __shfl_xor(wh, off));
+  }
+  int_tile_clip(v, g, dl, vc, zs, lane, zl, zh, wl, wh);
+  wl = __builtin_amdgcn_readfirstlane(wl);
+  wh = __builtin_amdgcn_readfirstlane(wh);
+  if (role == 1) {
+    if (lane == 0 && v.iwork) v.iwork[tile] = wh >= wl ? (unsigned)(wh - wl + 1) : 0u;
+    v.itab_zlh()[(size_t)tile * 64 + lane] = int2{zl, zh};
+  }
+  if (wh < wl) {
+    if (role == 1 && lane < nchunk) put(lane, 0, -1, 0ull, 0ull, zs);
+    return;
+  }
+  // lane c: chunk c's cuts
+  int cza = 0, czb = -1;
+  if (lane < nchunk) int_chunk(v, KFX_INT_CHUNKR, lane, nchunk, wl, wh, cza, czb);
+  if (role == 0) {
+    float *const rows = v.itab_vc() + (size_t)tile * nchunk * 192 + lane;
+    int z = 0;
+    for (int c = 0; c < nchunk; ++c) {
+      const int za = __builtin_amdgcn_readfirstlane(__shfl(cza, c)), zb = __builtin_amdgcn_readfirstlane(__shfl(czb, c));
+      const int zc = za & ~(KFX_INT_KB - 1);
+      vc = replay(vc, zs, z, zc);  // (cuts are monotone: zc >= z)
+      z = max(z, zc);
+      const bool live = min(zb, zh) >= max(za, zl);
+      if (__all(!live)) continue;
+      const bool fast = __all(!live || column_fast(vc, zs, v.Z));
+      rows[c * 192] = vc.x;
+      rows[c * 192 + 64] = vc.y;
+      rows[c * 192 + 128] = vc.z;
+      if (lane == 0) hdr[c].fast = fast ? 1 : 0;
+    }
+    return;
+  }
+  // lane c: whether chunk c has a live lane
+  bool cwork = false;
+  for (int c = 0; c < nchunk; ++c) {
+    const int za = __builtin_amdgcn_readfirstlane(__shfl(cza, c)), zb = __builtin_amdgcn_readfirstlane(__shfl(czb, c));
+    const bool work = !__all(!(min(zb, zh) >= max(za, zl)));
+    if (lane == c) cwork = work;
+  }
+  // certificates: one evaluation per brick of the interval
+  const uint8_t *const sett = v.settled ? v.settled + (size_t)tile * (v.bw * 64) - v.bz0 : nullptr;
+  ChunkMasks m;
+  const int b1 = wh >> 3;
+  for (int rb = wl >> 3; rb <= b1; rb += 64) {
+    const int b = rb + lane;
+    bool touched = false, inside = false;
+    for (int c = 0; c < nchunk; ++c) {
+      const int za = __builtin_amdgcn_readfirstlane(__shfl(cza, c)), zb = __builtin_amdgcn_readfirstlane(__shfl(czb, c));
+      if (!__builtin_amdgcn_readfirstlane(__shfl((int)cwork, c))) continue;
+      touched = touched || brick_touched(b, za, zb);
+      inside = inside || brick_inside(b, za, zb);
+    }
+    const bool isset = sett && b <= b1 && sett[b] != 0;
+    const unsigned cert =
+        touched ? brick_certificates(P.R, P.t, v.vs[0], v.vs[1], g.fx, g.fy, g.cx, g.cy, g.w, g.h, (tile % v.tiles_x) * 8,
+                                    (tile / v.tiles_x) * 8, b * 8, v.trunc, dmin_grid(dl, g), dmax_grid(dl, g),
+                                    isset && inside, (g.w + 15) >> 4, v.far_k, v.hid_k)
+                : 0u;
+    const unsigned long long hid = __ballot((cert & kBrickHidden) != 0u), fre = __ballot((cert & kBrickFree) != 0u),
+                             set = __ballot(isset);
+    if (cwork) chunk_masks_round(cza, czb, rb, hid, fre, set, m);
+  }
+  if (lane < nchunk) {
+    if (cwork) {
+      put(lane, cza, czb, m.skipm, m.setm, zs);
+      if (v.skipcnt && m.skipm) {  // debug counts: every brick of skipm is stepped over exactly once
+        const unsigned nf = (unsigned)__popcll(m.freem), nh = (unsigned)__popcll(m.skipm & ~m.freem);
+        if (nf) atomicAdd(v.skipcnt, (unsigned long long)nf);
+        if (nh) atomicAdd(v.skipcnt + 1, (unsigned long long)nh);
+        if (m.overm) atomicAdd(v.skipcnt + 2, (unsigned long long)__popcll(m.overm));
+      }
+    } else {
+      put(lane, 0, -1, 0ull, 0ull, zs);
+    }
   }
 }
 
@@ -2985,11 +3165,14 @@ static int integrate_mode(const VolView &v) {
   return v.zn >= KFX_INT_ADAPT_ZN && v.zn < KFX_INT_ADAPT_ZN_END ? 1 : 0;
 }
 
+// a whole volume in geometric chunks: the contexts that may keep a tile table
+static bool integrate_tab_kind(const VolView &v) { return integrate_mode(v) == 0 && v.zn == v.Z; }
+
 int integrate_chunks(const VolView &v) {
   const int tiles = v.tiles_x * v.tiles_y;
   if (integrate_mode(v) == 1) return std::max(1, std::min(KFX_INT_NC, v.zn / 32));  // chunks of >= 32 slices
   // z-chunks so that >= KFX_INT_WAVES waves exist (16 per SIMD on 1024 SIMDs)
-  int nc = (KFX_INT_WAVES + tiles - 1) / tiles;
+  int nc = ((integrate_tab_kind(v) ? KFX_INT_WAVES_TAB : KFX_INT_WAVES) + tiles - 1) / tiles;
   // Z-slabs (a context storing part of the volume's slices): also at most
   // ~KFX_INT_SLAB_CHUNK slices per chunk.  A slab's waves otherwise cover its
   // whole stored range (C4 slab 0: 344 slices, one chunk per tile: 6150
@@ -3001,6 +3184,12 @@ int integrate_chunks(const VolView &v) {
   if (KFX_INT_SLAB_CHUNK > 0 && v.zn < v.Z)
     nc = std::max(nc, std::min((v.zn + KFX_INT_SLAB_CHUNK - 1) / KFX_INT_SLAB_CHUNK, KFX_INT_SLAB_CAPW / tiles));
   return std::max(1, std::min(KFX_INT_MAXCHUNK, nc));
+}
+
+// the contexts whose integrate takes its prologue from the tile table
+// (k_int_tiles): a whole volume in geometric chunks, more than one per tile
+bool integrate_tiles(const VolView &v) {
+  return integrate_tab_kind(v) && integrate_chunks(v) > 1;
 }
 
 // Longest-first dispatch order of k_integrate's (tile, chunk) items for the
@@ -3080,6 +3269,10 @@ __global__ __launch_bounds__(1024) void k_int_order(const unsigned *__restrict__
   }
 }
 
+__global__ void k_zero_skipcnt(unsigned long long *n) {
+  if (threadIdx.x < 3) n[threadIdx.x] = 0ull;
+}
+
 void launch_integrate(hipStream_t s, VolView v, LevelGeom g0, const float2 *dl0, const float *dmap,
                       const float *invl, const uint8_t *bgr, DevState *st, DevPose *log, DevPose vpose,
                       const float *xpose, unsigned long long *counters, bool order) {
@@ -3089,6 +3282,9 @@ void launch_integrate(hipStream_t s, VolView v, LevelGeom g0, const float2 *dl0,
   v.iadapt = integrate_mode(v);
   if (!v.iadapt) v.iperm = nullptr, v.iwork = nullptr;  // geometric chunks in block order
   if (counters) v.iwork = nullptr;  // the count-only pass leaves the order alone
+  // the tile table (k_int_tiles) where the context keeps one: geometric chunks,
+  // more than one per tile, a whole volume (integrate_tiles); else the waves' own prologue
+  if (counters || !integrate_tiles(v)) v.itab = nullptr;
   dim3 grd(tiles * nchunk);  // one wave (block) per (tile, chunk) item
   const bool idx32 = !v.force64 && v.local_voxels() < (1ull << 31);  // 32-bit tsdf/weight byte offsets
 #ifdef KFX_INT_TRACE
@@ -3100,18 +3296,28 @@ void launch_integrate(hipStream_t s, VolView v, LevelGeom g0, const float2 *dl0,
   g_int_trace_waves = (int)grd.x;
   (void)hipMemsetAsync(trace_buf, 0, sizeof(unsigned long long) * 4 * g_int_trace_waves, s);  // waves that exit early write none
   if (!counters) {
-    hipLaunchKernelGGL((k_integrate<false, true>), grd, dim3(KFX_INT_BLOCK), 0, s, v, g0, dl0, dmap, invl, bgr, st,
-                       log, vpose, xpose, trace_buf);
+    if (v.itab) hipLaunchKernelGGL(k_int_tiles, dim3(tiles), dim3(128), 0, s, v, g0, dl0, st, vpose, xpose);
+    if (v.itab)
+      hipLaunchKernelGGL((k_integrate<false, true, true>), grd, dim3(KFX_INT_BLOCK), 0, s, v, g0, dl0, dmap, invl, bgr, st,
+                         log, vpose, xpose, trace_buf);
+    else
+      hipLaunchKernelGGL((k_integrate<false, true>), grd, dim3(KFX_INT_BLOCK), 0, s, v, g0, dl0, dmap, invl, bgr, st,
+                         log, vpose, xpose, trace_buf);
     return;
   }
 #endif
-#define KFX_LAUNCH_INT(C, I)                                                                             \
-  hipLaunchKernelGGL((k_integrate<C, I>), grd, dim3(KFX_INT_BLOCK), 0, s, v, g0, dl0, dmap, invl, bgr, st, log, vpose, xpose, \
+#define KFX_LAUNCH_INT(C, I, T)                                                                          \
+  hipLaunchKernelGGL((k_integrate<C, I, T>), grd, dim3(KFX_INT_BLOCK), 0, s, v, g0, dl0, dmap, invl, bgr, st, log, vpose, xpose, \
                      counters)
-  if (!counters && v.skipcnt) (void)hipMemsetAsync(v.skipcnt, 0, 24, s);  // debug: this launch's skipped bricks
-  if (counters) KFX_LAUNCH_INT(true, false);
-  else if (idx32) KFX_LAUNCH_INT(false, true);
-  else KFX_LAUNCH_INT(false, false);
+  // debug: this launch's skipped bricks, zeroed by a kernel (as a 24-byte memset node of a captured
+  // frame the reset left an address-like value behind in processes that had run many other contexts)
+  if (!counters && v.skipcnt) hipLaunchKernelGGL(k_zero_skipcnt, dim3(1), dim3(64), 0, s, v.skipcnt);
+  if (v.itab) hipLaunchKernelGGL(k_int_tiles, dim3(tiles), dim3(128), 0, s, v, g0, dl0, st, vpose, xpose);
+  if (counters) KFX_LAUNCH_INT(true, false, false);
+  else if (idx32 && v.itab) KFX_LAUNCH_INT(false, true, true);
+  else if (idx32) KFX_LAUNCH_INT(false, true, false);
+  else if (v.itab) KFX_LAUNCH_INT(false, false, true);
+  else KFX_LAUNCH_INT(false, false, false);
 #undef KFX_LAUNCH_INT
   if (!counters && order) launch_int_order(s, v);
 }

@@ -40,7 +40,7 @@ EXPORTS = [
     "kfx_extract_points_attr", "kfx_extract_mesh_attr", "kfx_write_ply_attr", "kfx_write_ply_mesh_attr",
     "kfx_save_pointcloud_attr", "kfx_save_mesh_attr",
     "kfx_render_view", "kfx_get_view_ms", "kfx_write_ppm",
-    "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden",
+    "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
@@ -90,6 +90,7 @@ def lib():
         "kfx_debug_force_icp_stall": ([vp], i),
         "kfx_debug_force_index64": ([vp, i], i),
         "kfx_debug_count_settled": ([vp, i], i),
+        "kfx_debug_int_tiles": ([vp, i], i),
         "kfx_debug_get_settled": ([vp, P(C.c_uint64)], i),
         "kfx_debug_get_hidden": ([vp, P(C.c_uint64)], i),
         "kfx_debug_icp_band_ms": ([vp, i, i, i, P(C.c_float)], i),
@@ -517,6 +518,13 @@ class KinectFusion:
     def debug_count_settled(self, on=True):
         """Debug hook: integrate counts the settled bricks its waves skip."""
         _check(lib().kfx_debug_count_settled(self._h, int(on)), "kfx_debug_count_settled")
+
+    def debug_int_tiles(self, on=True) -> bool:
+        """Debug switch: integrate's per-frame tile kernel on / off (off: every wave
+        computes its own prologue); returns whether it is in use."""
+        r = lib().kfx_debug_int_tiles(self._h, int(on))
+        _check(min(r, 0), "kfx_debug_int_tiles")
+        return bool(r)
 
     def debug_get_settled(self):
         """(bricks whose settled byte is set, bricks skipped by the last integrate)."""
