@@ -460,6 +460,59 @@ int kfx_write_ply_mesh_attr(const char *path, const kfx_vertex *v, int64_t n_tri
 int kfx_save_pointcloud_attr(kfx_ctx *ctx, const char *path, int64_t cap);
 int kfx_save_mesh_attr(kfx_ctx *ctx, const char *path, int64_t cap_tris);
 
+/* ---- moving volume ----------------------------------------
+ * Added under ABI version 2, nothing else changed.  The TSDF window follows
+ * the camera: kfx_shift_volume moves the contents by whole bricks inside
+ * device memory and moves the volume pose the other way, so the model stays
+ * where it is in the world; kfx_evict_points hands out the surface the shift
+ * is about to drop.  A context that never shifts behaves as before.
+ *
+ * kfx_shift_volume: shift = (sx, sy, sz) voxels along the volume's own axes,
+ * each a multiple of 8.  Afterwards voxel (x, y, z) holds what voxel (x + sx,
+ * y + sy, z + sz) held, where that index lies inside the volume; every other
+ * voxel is empty as after a reset (tsdf 0, weight 0, colour 0).  A component
+ * with |s| >= its dimension empties the volume.  The voxel origin becomes
+ * o' = o + s and the volume pose R' = R0, t' = t0 + R0 (o' * voxel_size),
+ * R0, t0 the pose the context was created with (recomputed from t0 each time:
+ * rounding does not accumulate), in float32 without contraction, in this
+ * order: d_k = (float)o'_k * vs_k (vs_k = volu_range[k] / (float)volu_dims[k]);
+ * row sum (R[3i]*d0 + R[3i+1]*d1) + R[3i+2]*d2; t'_i = t0_i + sum.  Every later
+ * call uses the new pose (frames, kfx_render_view, the extractors,
+ * kfx_slice_work*).  The call runs on the context's stream behind every queued
+ * frame (staged and overlapped ones included) and in front of every later one;
+ * captured graphs are dropped and recaptured.  The skip maps of raycast and
+ * integrate are rebuilt from the new contents, as after kfx_upload_tsdf.  The
+ * previous-frame maps, the pose record (world coordinates), the frame count
+ * and a pending tracking status are untouched.  A zero shift does nothing.
+ * KFX_ERR_ARG: a null shift or a component that is no multiple of 8 (volume,
+ * origin and pose untouched).  KFX_ERR_STATE: a slab context of a world larger
+ * than 1 (a z shift across slabs would need an exchange: out of scope).
+ * kfx_reset also returns the origin to (0, 0, 0) and the pose to (R0, t0).  A
+ * tracking-loss reset happens on the device and cannot: on KFX_TRACKING_LOST
+ * call kfx_reset before going on with a context that has shifted.
+ *
+ * kfx_evict_points: the items of kfx_extract_points_attr whose grid edge a -> b
+ * has a or b outside the box the shift would keep (voxel v is kept iff
+ * 0 <= v_k - s_k < dims_k for every k), in the same canonical order and with
+ * the same 28 bytes (gradient and colour computed on the whole volume as it
+ * stands).  Evicted items and the items of the kept box partition the full
+ * extraction.  The volume is not changed.  Writes min(cap, total) items, *n =
+ * total, cap = 0 counts only; a zero shift gives 0 items.  Same argument
+ * checks as kfx_shift_volume; blocks until the items are on the host.
+ *
+ * kfx_shift_for_pose (host only, no context): the shift that centres the
+ * volume on the point ahead_m metres along the camera's +z: c = cam_pose (0, 0,
+ * ahead_m), q = volume_pose^-1 c, shift_k = 8 lround(((q_k - range_k/2) / vs_k)
+ * / 8), in double.  KFX_ERR_ARG: a null pointer, a non-finite pose entry, a
+ * non-finite or negative ahead_m. */
+int kfx_shift_volume(kfx_ctx *ctx, const int shift[3]);
+int kfx_evict_points(kfx_ctx *ctx, const int shift[3], kfx_vertex *out, int64_t cap, int64_t *n);
+int kfx_get_volume_origin(kfx_ctx *ctx, int origin[3]);   /* accumulated shift, voxels */
+int kfx_get_volume_pose(kfx_ctx *ctx, kfx_pose *out);     /* the volume pose in effect */
+int kfx_get_shift_ms(kfx_ctx *ctx, float out_ms[2]);      /* device ms of the last evict, last shift (HIP events) */
+int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *volume_pose, const kfx_pose *cam_pose,
+                       float ahead_m, int shift[3]);      /* host only, no context */
+
 /* ---- dataset front-end (host only; no GPU needed) --------------------------
  * depth_sensor in its DATASET build (depth_sensor.cpp:11-46 open, :186-196
  * getFrame) without OpenCV: the PNG files of `<dir>/color` and `<dir>/depth` in

@@ -237,6 +237,13 @@ struct kfx_ctx {
   size_t view_out_cap = 0, view_maps_cap = 0;
   hipEvent_t ev_view[2]{};
   float view_ms = 0.f;            // device time of the last view's launch
+  // moving volume: the pose the context was created with, the
+  // accumulated shift in voxels (p.volu_pose is derived from both), and the
+  // events around the last eviction's passes [0, 1] and the last shift [2, 3]
+  kfx_pose volu_pose0{};
+  int origin[3] = {0, 0, 0};
+  hipEvent_t ev_shift[4]{};
+  bool shift_timed[2] = {false, false};
   uint8_t *mc_tab = nullptr;      // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded
@@ -975,6 +982,29 @@ int do_reset(kfx_ctx *c) {
   return KFX_OK;
 }
 
+// The volume pose of voxel origin o: R = R0, t = t0 + R0 (o * vs),
+// from the creation pose each time, in float32 without contraction:
+// d_k = (float)o_k * vs_k, row sum (R[3i] d0 + R[3i+1] d1) + R[3i+2] d2, then
+// t0_i + sum.  Every later launch reads c->p.volu_pose; the ICP plans hold a
+// copy and captured graphs bake it in: the caller has both streams idle.
+void set_volume_origin(kfx_ctx *c, const int o[3]) {
+  float d[3];
+  for (int k = 0; k < 3; ++k) {
+    c->origin[k] = o[k];
+    d[k] = (float)o[k] * c->vol.vs[k];
+  }
+  const kfx_pose &p0 = c->volu_pose0;
+  c->p.volu_pose = p0;
+  for (int i = 0; i < 3; ++i) {
+    const float a = p0.R[3 * i] * d[0], b = p0.R[3 * i + 1] * d[1], e = p0.R[3 * i + 2] * d[2];
+    const float sum = (a + b) + e;
+    c->p.volu_pose.t[i] = p0.t[i] + sum;
+  }
+  for (int b = 0; b < 2; ++b) c->planb[b].vpose = to_dev(c->p.volu_pose);
+  c->icp_plan.vpose = to_dev(c->p.volu_pose);
+  destroy_graphs(c);
+}
+
 int check_ctx(kfx_ctx *c) {
   if (!c) return set_err(KFX_ERR_ARG, "null context");
   c->api_seq += 1;
@@ -1151,6 +1181,7 @@ static int create_impl(const kfx_intrinsics *intr, const kfx_params *params, int
   c->world = world;
   c->intr = *intr;
   c->p = p;
+  c->volu_pose0 = p.volu_pose;
   c->L = p.pyramid_height;
   c->icp_exact_pixels = icp_exact;
   for (int l = 0; l < c->L; ++l) c->g[l] = level_geom(*intr, l);
@@ -1297,6 +1328,8 @@ int kfx_destroy(kfx_ctx *c) {
   if (c->view_maps) (void)hipFree(c->view_maps);
   for (hipEvent_t e : c->ev_view)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_shift)
+    if (e) (void)hipEventDestroy(e);
   for (auto &e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {c->ev_prep, c->ev_free[0], c->ev_free[1], c->ev_icp, c->ev_group})
@@ -1319,6 +1352,8 @@ int kfx_reset(kfx_ctx *c) {
   if (c->cstream) HIPCHK(hipStreamSynchronize(c->cstream));
   HIPCHK(hipStreamSynchronize(c->pstream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  const int zero[3] = {0, 0, 0};
+  if (c->origin[0] || c->origin[1] || c->origin[2]) set_volume_origin(c, zero);  // (the streams are idle)
   return do_reset(c);
 }
 
@@ -3143,6 +3178,148 @@ int kfx_slab_frame_finish(kfx_ctx *c, const uint32_t *payload) {
   HIPCHK(hipGetLastError());
   c->pending += 1;
   return finish_frame(c);
+}
+
+// ---- moving volume -------------------------------------------
+
+// the checks kfx_shift_volume and kfx_evict_points share
+static int shift_args(kfx_ctx *c, const int shift[3]) {
+  if (!shift) return set_err(KFX_ERR_ARG, "null shift");
+  for (int k = 0; k < 3; ++k)
+    if (shift[k] % 8) return set_err(KFX_ERR_ARG, "shift components must be multiples of 8 voxels (whole bricks)");
+  if (c->slab && c->world > 1)
+    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
+  return KFX_OK;
+}
+
+int kfx_shift_volume(kfx_ctx *c, const int shift[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = shift_args(c, shift))) return r;
+  if (!shift[0] && !shift[1] && !shift[2]) return KFX_OK;
+  for (hipEvent_t &e : c->ev_shift)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  // the frames queued so far run at the old pose: captured graphs hold it as
+  // a kernel argument, so they finish before the graphs are dropped
+  HIPCHK(hipStreamSynchronize(c->pstream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  // the move, and with it the state an upload of the shifted records leaves:
+  // both skip maps rebuilt from the new contents, no settled byte, the gate
+  // open
+  HIPCHK(hipEventRecord(c->ev_shift[2], c->stream));
+  launch_shift(c->stream, c->vol, shift);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_shift[3], c->stream));
+  c->shift_timed[1] = true;
+  int o[3];
+  for (int k = 0; k < 3; ++k) o[k] = c->origin[k] + shift[k];
+  set_volume_origin(c, o);
+  return KFX_OK;
+}
+
+int kfx_evict_points(kfx_ctx *c, const int shift[3], kfx_vertex *out, int64_t cap, int64_t *n) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = shift_args(c, shift))) return r;
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad point buffer");
+  for (hipEvent_t &e : c->ev_shift)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const size_t units = evict_units(c->vol, shift);
+  int64_t total = 0;
+  HIPCHK(hipEventRecord(c->ev_shift[0], c->stream));
+  if (units > 0) {
+    const size_t nb = scan_blocks(units);
+    char *ws = nullptr;
+    const size_t o_off = (units * 4 + 7) & ~(size_t)7;
+    HIPCHK(hipMalloc(&ws, o_off + units * 8 + nb * 8 + 64));
+    unsigned *counts = (unsigned *)ws;
+    unsigned long long *offsets = (unsigned long long *)(ws + o_off);
+    unsigned long long *bsum = offsets + units;
+    unsigned long long *dtot = bsum + nb;
+    const DevPose vp = to_dev(c->p.volu_pose);
+    launch_evict(c->stream, c->vol, vp, shift, counts, nullptr, nullptr, 0);
+    launch_scan(c->stream, counts, offsets, bsum, units, dtot);
+    unsigned long long ht = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    total = (int64_t)ht;
+    const int64_t m = std::min<int64_t>(total, cap);
+    float *dout = nullptr;
+    if (e == hipSuccess && m > 0) {
+      e = hipMalloc(&dout, (size_t)m * sizeof(kfx_vertex));
+      if (e == hipSuccess) {
+        launch_evict(c->stream, c->vol, vp, shift, counts, offsets, dout, (unsigned long long)m);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(c->ev_shift[1], c->stream);
+        if (e == hipSuccess)
+          e = hipMemcpyAsync(out, dout, (size_t)m * sizeof(kfx_vertex), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(dout);
+      }
+    } else if (e == hipSuccess) {
+      e = hipEventRecord(c->ev_shift[1], c->stream);
+    }
+    (void)hipFree(ws);
+    if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("evict_points: ") + hipGetErrorString(e));
+  } else {
+    HIPCHK(hipEventRecord(c->ev_shift[1], c->stream));
+  }
+  c->shift_timed[0] = true;
+  if (n) *n = total;
+  return KFX_OK;
+}
+
+int kfx_get_volume_origin(kfx_ctx *c, int origin[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!origin) return set_err(KFX_ERR_ARG, "null origin");
+  for (int k = 0; k < 3; ++k) origin[k] = c->origin[k];
+  return KFX_OK;
+}
+
+int kfx_get_volume_pose(kfx_ctx *c, kfx_pose *out) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out) return set_err(KFX_ERR_ARG, "null pose");
+  *out = c->p.volu_pose;
+  return KFX_OK;
+}
+
+int kfx_get_shift_ms(kfx_ctx *c, float out_ms[2]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  for (int k = 0; k < 2; ++k) {
+    out_ms[k] = 0.f;
+    if (!c->shift_timed[k]) continue;
+    HIPCHK(hipEventSynchronize(c->ev_shift[2 * k + 1]));
+    HIPCHK(hipEventElapsedTime(&out_ms[k], c->ev_shift[2 * k], c->ev_shift[2 * k + 1]));
+  }
+  return KFX_OK;
+}
+
+int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *vp, const kfx_pose *cam, float ahead_m, int shift[3]) {
+  if (!p || !vp || !cam || !shift) return set_err(KFX_ERR_ARG, "null argument");
+  if (!std::isfinite(ahead_m) || ahead_m < 0.f) return set_err(KFX_ERR_ARG, "ahead_m must be finite and >= 0");
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? vp->R[i] : vp->t[i - 9]) || !std::isfinite(i < 9 ? cam->R[i] : cam->t[i - 9]))
+      return set_err(KFX_ERR_ARG, "non-finite pose entry");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(p->volu_range[k]) || p->volu_range[k] <= 0.f || p->volu_dims[k] < 1)
+      return set_err(KFX_ERR_ARG, "volume range and dims must be positive");
+  double cw[3], q[3];
+  for (int i = 0; i < 3; ++i) cw[i] = (double)cam->R[3 * i + 2] * (double)ahead_m + (double)cam->t[i];
+  for (int j = 0; j < 3; ++j) {  // q = R_v^T (c - t_v)
+    q[j] = 0.0;
+    for (int i = 0; i < 3; ++i) q[j] += (double)vp->R[3 * i + j] * (cw[i] - (double)vp->t[i]);
+  }
+  for (int k = 0; k < 3; ++k) {
+    const double vs = (double)p->volu_range[k] / (double)p->volu_dims[k];
+    shift[k] = 8 * (int)std::lround(((q[k] - (double)p->volu_range[k] / 2.0) / vs) / 8.0);
+  }
+  return KFX_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip,
-// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip) and the host runtime (kfx_api.hip).  Not part of the public ABI.
+// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip) and the host runtime (kfx_api.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -396,6 +396,22 @@ void launch_render(hipStream_t s, const float *vmap, const float *nmap, int n, c
 // vmap / nmap (float3) and ts (Ts of the hit, 0: none) are stored when non-null
 void launch_view(hipStream_t s, VolView v, LevelGeom g, DevPose cam2vol, const float eye[3], int type, uint8_t *out,
                  float *vmap, float *nmap, float *ts);
+
+// ---- kfx_shift.hip --------------------------------------------------------
+// the moving volume, whole single volumes only.  shift: voxels
+// per axis, every component a multiple of 8.
+// In place: voxel (x, y, z) <- voxel (x + sx, y + sy, z + sz) where that lies
+// in the volume, else 0 (tsdf, weight and colour); no temporary memory.  The
+// occupancy maps, settled bytes and gate are left as launch_occ_rebuild
+// leaves them for the new contents.
+void launch_shift(hipStream_t s, const VolView &v, const int shift[3]);
+// units (bricks) the eviction passes visit: entries of counts / offsets
+size_t evict_units(const VolView &v, const int shift[3]);
+// the attributed points (7 words) of launch_extract whose grid edge has an end
+// the shift drops, in the same order: offsets == null counts per unit, else
+// writes them at offsets (< cap)
+void launch_evict(hipStream_t s, const VolView &v, DevPose vpose, const int shift[3], unsigned *counts,
+                  const unsigned long long *offsets, float *out, unsigned long long cap);
 
 // ---- kfx_volume_io.hip ----------------------------------------------------
 void launch_export_records(hipStream_t s, VolView v, int z0, int nz, uint64_t *dst);

@@ -3,8 +3,12 @@
 // getFrame → kinectfusion::pipeline per frame → poses.txt (and optionally the
 // point cloud PLY, main.cpp:43-44; the coloured, oriented cloud and mesh are
 // extensions: kfx_save_pointcloud_attr / kfx_save_mesh_attr; view.ppm is the
-// fused colour rendered from the last tracked pose, kfx_render_view).
+// fused colour rendered from the last tracked pose, kfx_render_view;
+// followed_cloud.ply makes the volume follow the camera, kfx_shift_for_pose /
+// kfx_evict_points / kfx_shift_volume after every frame, and holds the evicted
+// points followed by the final cloud).
 //   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
+//                  [followed_cloud.ply]
 #include <chrono>
 #include <cstdio>
 #include <vector>
@@ -14,7 +18,8 @@
 int main(int argc, char **argv) {
   if (argc < 2) {
     std::fprintf(stderr,
-                 "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]\n",
+                 "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm] "
+                 "[followed_cloud.ply]\n",
                  argv[0]);
     return 2;
   }
@@ -42,6 +47,10 @@ int main(int argc, char **argv) {
   std::vector<uint8_t> bgr((size_t)intr.width * intr.height * 3);
   std::vector<float> depth((size_t)intr.width * intr.height);
   double gpu_s = 0;
+  const bool follow = argc > 7;  // the volume follows the camera
+  const float ahead = 0.5f + p.volu_range[2] / 2;
+  std::vector<kfx_vertex> evicted;
+  int shifts = 0;
   for (int k = 0; k < n; ++k) {
     if (kfx_dataset_read(ds, k, bgr.data(), depth.data()) != KFX_OK) {
       std::printf("no image! (%s)\n", kfx_last_error());
@@ -56,6 +65,35 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "error: %s\n", kfx_last_error());
       return 1;
     }
+    if (!follow) continue;
+    if (r == KFX_TRACKING_LOST) {  // the device reset cannot move the volume back: kfx.h
+      if (kfx_reset(ctx) != KFX_OK) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      continue;
+    }
+    kfx_pose vol, cam;
+    int s[3] = {0, 0, 0};
+    int64_t ne = 0;
+    if (kfx_get_volume_pose(ctx, &vol) != KFX_OK || kfx_get_cur_camera_pose(ctx, &cam) != KFX_OK ||
+        kfx_shift_for_pose(&p, &vol, &cam, ahead, s) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    if (!s[0] && !s[1] && !s[2]) continue;
+    if (kfx_evict_points(ctx, s, nullptr, 0, &ne) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    const size_t at = evicted.size();
+    evicted.resize(at + (size_t)ne);
+    if ((ne > 0 && kfx_evict_points(ctx, s, evicted.data() + at, ne, &ne) != KFX_OK) ||
+        kfx_shift_volume(ctx, s) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    ++shifts;
   }
   int frames = 0;
   kfx_get_frame_count(ctx, &frames);
@@ -63,13 +101,14 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "error: %s\n", kfx_last_error());
     return 1;
   }
-  if ((argc > 3 && kfx_save_pointcloud(ctx, argv[3], 0) != KFX_OK) ||
-      (argc > 4 && kfx_save_pointcloud_attr(ctx, argv[4], 0) != KFX_OK) ||
-      (argc > 5 && kfx_save_mesh_attr(ctx, argv[5], 0) != KFX_OK)) {
+  // (an empty name skips that output, so a later one can be asked for alone)
+  if ((argc > 3 && argv[3][0] && kfx_save_pointcloud(ctx, argv[3], 0) != KFX_OK) ||
+      (argc > 4 && argv[4][0] && kfx_save_pointcloud_attr(ctx, argv[4], 0) != KFX_OK) ||
+      (argc > 5 && argv[5][0] && kfx_save_mesh_attr(ctx, argv[5], 0) != KFX_OK)) {
     std::fprintf(stderr, "error: %s\n", kfx_last_error());
     return 1;
   }
-  if (argc > 6) {  // the fused colour seen from the last tracked pose, at the dataset's intrinsics
+  if (argc > 6 && argv[6][0]) {  // the fused colour seen from the last tracked pose, at the dataset's intrinsics
     kfx_pose last;
     std::vector<uint8_t> img((size_t)intr.width * intr.height * 3);
     if (kfx_get_cur_camera_pose(ctx, &last) != KFX_OK ||
@@ -78,6 +117,22 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "error: %s\n", kfx_last_error());
       return 1;
     }
+  }
+  if (follow) {  // what left the volume, then what is in it
+    int64_t nf = 0;
+    const size_t at = evicted.size();
+    if (kfx_extract_points_attr(ctx, nullptr, 0, &nf) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    evicted.resize(at + (size_t)nf);
+    if ((nf > 0 && kfx_extract_points_attr(ctx, evicted.data() + at, nf, &nf) != KFX_OK) ||
+        kfx_write_ply_attr(argv[7], evicted.data(), (int64_t)evicted.size()) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    std::printf("followed: %d shifts, %lld evicted points, %lld in the volume\n", shifts, (long long)at,
+                (long long)nf);
   }
   std::printf("end! %d frames, frame_count %d, %.3f ms/frame in kfx_pipeline (host frames, PCIe incl.)\n", n,
               frames, n ? 1e3 * gpu_s / n : 0.0);

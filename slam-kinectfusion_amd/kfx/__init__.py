@@ -20,7 +20,7 @@ from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, Intr
 
 __all__ = ["KinectFusion", "KfxError", "Dataset", "png_info", "png_read_bgr8", "png_read_depth", "parse_intr",
            "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "write_ply_attr", "write_ply_mesh_attr",
-           "write_ppm", "VIEW_KINDS", "VERTEX_DTYPE", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
+           "write_ppm", "shift_for_pose", "VIEW_KINDS", "VERTEX_DTYPE", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
            "default_params", "KFX_FRAME_CUR", "KFX_FRAME_PREV", "KFX_OK", "KFX_TRACKING_LOST", "EXPORTS"]
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,6 +40,8 @@ EXPORTS = [
     "kfx_extract_points_attr", "kfx_extract_mesh_attr", "kfx_write_ply_attr", "kfx_write_ply_mesh_attr",
     "kfx_save_pointcloud_attr", "kfx_save_mesh_attr",
     "kfx_render_view", "kfx_get_view_ms", "kfx_write_ppm",
+    "kfx_shift_volume", "kfx_evict_points", "kfx_get_volume_origin", "kfx_get_volume_pose", "kfx_get_shift_ms",
+    "kfx_shift_for_pose",
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
@@ -143,6 +145,12 @@ def lib():
         "kfx_render_view": ([vp, P(Intrinsics), P(Pose), i, P(C.c_uint8), P(f), P(f), P(f)], i),
         "kfx_get_view_ms": ([vp, P(f)], i),
         "kfx_write_ppm": ([C.c_char_p, P(C.c_uint8), i, i], i),
+        "kfx_shift_volume": ([vp, P(i)], i),
+        "kfx_evict_points": ([vp, P(i), vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_get_volume_origin": ([vp, P(i)], i),
+        "kfx_get_volume_pose": ([vp, P(Pose)], i),
+        "kfx_get_shift_ms": ([vp, P(f)], i),
+        "kfx_shift_for_pose": ([P(Params), P(Pose), P(Pose), f, P(i)], i),
         "kfx_volume_checksum": ([vp, P(C.c_uint64)], i),
         "kfx_write_ply": ([C.c_char_p, P(f), C.c_int64], i),
         "kfx_save_pointcloud": ([vp, C.c_char_p, C.c_int64], i),
@@ -223,6 +231,17 @@ def write_ppm(path: str, bgr: np.ndarray):
     assert img.ndim == 3 and img.shape[2] == 3
     _check(lib().kfx_write_ppm(path.encode(), img.ctypes.data_as(C.POINTER(C.c_uint8)), img.shape[1], img.shape[0]),
            "kfx_write_ppm")
+
+
+def shift_for_pose(params: Params, volume_pose, cam_pose, ahead_m: float) -> tuple:
+    """kfx_shift_for_pose: the (sx, sy, sz) voxel shift (multiples of 8) that centres the
+    volume at `volume_pose` on the point ahead_m metres along the +z of camera-to-world
+    `cam_pose` (4x4 matrices or Pose).  Host only."""
+    V = volume_pose if isinstance(volume_pose, Pose) else Pose.from_matrix(volume_pose)
+    K = cam_pose if isinstance(cam_pose, Pose) else Pose.from_matrix(cam_pose)
+    s = (C.c_int * 3)()
+    _check(lib().kfx_shift_for_pose(C.byref(params), C.byref(V), C.byref(K), float(ahead_m), s), "kfx_shift_for_pose")
+    return tuple(int(x) for x in s)
 
 
 # kfx_vertex (include/kfx.h): position, unit normal, colour in the ABI's BGR order + a (255: coloured)
@@ -641,6 +660,50 @@ class KinectFusion:
         ms = C.c_float()
         _check(lib().kfx_get_view_ms(self._h, C.byref(ms)), "kfx_get_view_ms")
         return float(ms.value)
+
+    # ---- moving volume ------------------------------------
+    def shift_volume(self, shift):
+        """kfx_shift_volume: move the volume's contents by `shift` = (sx, sy, sz) voxels
+        (multiples of 8) in place, and the volume pose with them; None passes a null shift."""
+        s = None if shift is None else (C.c_int * 3)(*[int(x) for x in shift])
+        _check(lib().kfx_shift_volume(self._h, s), "kfx_shift_volume")
+
+    def evict_points(self, shift, cap: int = 10_000_000) -> np.ndarray:
+        """kfx_evict_points: the items of extract_points_attr that `shift` would drop,
+        (N,) VERTEX_DTYPE in the same order; the volume is unchanged."""
+        s = None if shift is None else (C.c_int * 3)(*[int(x) for x in shift])
+        n = C.c_int64()
+        out = np.empty(max(cap, 0), np.dtype(VERTEX_DTYPE))
+        _check(lib().kfx_evict_points(self._h, s, out.ctypes.data_as(C.c_void_p) if cap > 0 else None, max(cap, 0),
+                                      C.byref(n)), "kfx_evict_points")
+        return _trim(out, min(n.value, max(cap, 0)))
+
+    def evict_count(self, shift) -> int:
+        """Items evict_points(shift) would return (count pass only)."""
+        s = (C.c_int * 3)(*[int(x) for x in shift])
+        n = C.c_int64()
+        _check(lib().kfx_evict_points(self._h, s, None, 0, C.byref(n)), "kfx_evict_points")
+        return n.value
+
+    @property
+    def volume_origin(self) -> tuple:
+        """The accumulated shift in voxels (kfx_get_volume_origin)."""
+        o = (C.c_int * 3)()
+        _check(lib().kfx_get_volume_origin(self._h, o), "kfx_get_volume_origin")
+        return tuple(int(x) for x in o)
+
+    @property
+    def volume_pose(self) -> np.ndarray:
+        """The volume pose in effect, 4x4 (kfx_get_volume_pose)."""
+        p = Pose()
+        _check(lib().kfx_get_volume_pose(self._h, C.byref(p)), "kfx_get_volume_pose")
+        return p.matrix()
+
+    def shift_ms(self) -> dict:
+        """Device ms of the last evict_points and the last shift_volume (HIP events)."""
+        a = (C.c_float * 2)()
+        _check(lib().kfx_get_shift_ms(self._h, a), "kfx_get_shift_ms")
+        return {"evict": a[0], "shift": a[1]}
 
     def extract_mesh(self, cap: int = 50_000_000) -> np.ndarray:
         """Marching-cubes triangles, (N, 3, 3) float32 world coordinates (canonical order)."""

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Device time of the moving volume on the bench's C2 workload
+(640x480, 512^3 @ 4 mm): after 30 frames of the bench's sequence, for each of
+the shifts (0,0,8), (8,0,0), (0,8,0), (8,8,8) and (0,0,64): kfx_evict_points
+(all of them first: it changes nothing), then kfx_shift_volume followed by the
+restoring shift (which brings the pose back; the dropped slab stays empty, and
+the time of the move does not depend on the contents), 5 repetitions after one
+warm-up, HIP-event ms from kfx_get_shift_ms.  For comparison the only route without it, in the same
+process: download_tsdf + upload_tsdf wall time (a new context with another
+volu_pose comes on top).  Bytes moved = 7 bytes read and 7 written per voxel
+that has a source in the volume, 7 written per cleared voxel (the occupancy
+rebuild reads the 2-byte tsdf once more; it is part of the timed span).
+Prints one JSON record.
+usage: [KFX_LIB_PATH=...] python3 tools/shift_bench.py [out.json [parent commit]]"""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.join(ROOT, "slam-kinectfusion_amd"))
+import kfx  # noqa: E402
+from kfx import synth  # noqa: E402
+from kfx.abi import Intrinsics, default_params  # noqa: E402
+
+WARM_FRAMES, REPS = 30, 5
+SHIFTS = ((0, 0, 8), (8, 0, 0), (0, 8, 0), (8, 8, 8), (0, 0, 64))
+COPY_TBS = 6.29  # the measured device copy rate the floor is derived from
+N = 512
+
+
+def stats(xs):
+    xs = sorted(float(x) for x in xs)
+    return {"min": xs[0], "median": xs[len(xs) // 2], "max": xs[-1], "all": xs}
+
+
+def main():
+    intr = synth.Intrinsics.vga()
+    p = default_params(dims=N, range_m=2.048)
+    bgr, dep, _ = synth.sequence(48, intr, L=2.048, noise=True, traj_seed=7, dropout=0.005)
+    kf = kfx.KinectFusion(Intrinsics.from_any(intr), p)
+    kf.stage_frames(bgr, dep.astype(np.float32))
+    for i in synth.ping_pong(48, WARM_FRAMES):
+        kf.pipeline_staged(int(i))
+    kf.synchronize()
+    nvox = N ** 3
+    rec, evicted, evict_ms = {}, {}, {}
+    for s in SHIFTS:  # every eviction before the first shift: it changes nothing, and the slabs still hold their surfaces
+        ev, items = [], 0
+        for r in range(REPS + 1):  # the first repetition warms up (first use creates the events, loads the kernels)
+            items = len(kf.evict_points(s))
+            if r:
+                ev.append(kf.shift_ms()["evict"])
+        evicted[str(s)], evict_ms[str(s)] = items, stats(ev)
+    for s in SHIFTS:
+        back = tuple(-x for x in s)
+        kept = int(np.prod([N - abs(x) for x in s]))
+        moved = 14 * kept + 7 * (nvox - kept)
+        sh = []
+        for r in range(REPS + 1):
+            kf.shift_volume(s)
+            ms = kf.shift_ms()["shift"]
+            kf.shift_volume(back)
+            if r:
+                sh.append(ms)
+        e, h, items = evict_ms[str(s)], stats(sh), evicted[str(s)]
+        tbs = moved / (h["median"] * 1e-3) / 1e12
+        rec[str(s)] = {"evict_ms": e, "evicted_items": items, "shift_ms": h, "bytes_moved": moved,
+                       "achieved_TBps": tbs, "fraction_of_copy_rate": tbs / COPY_TBS,
+                       "floor_ms_at_copy_rate": moved / (COPY_TBS * 1e12) * 1e3}
+    assert kf.volume_origin == (0, 0, 0)
+    route = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        r = kf.download_tsdf()
+        t1 = time.perf_counter()
+        kf.upload_tsdf(r)
+        t2 = time.perf_counter()
+        route.append({"download_ms": (t1 - t0) * 1e3, "upload_ms": (t2 - t1) * 1e3, "total_ms": (t2 - t0) * 1e3})
+    kf.close()
+    commit = sys.argv[2] if len(sys.argv) > 2 else ""  # (a copy of the tree without its history: give it)
+    if not commit:
+        try:
+            commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True,
+                                    text=True).stdout.strip()
+        except OSError:
+            pass
+    out = {
+        "workload": "C2 640x480, 512^3 @ 4 mm, %d frames of the bench sequence (ping-pong over 48)" % WARM_FRAMES,
+        "unit": "ms, device time between HIP events around the launches (kfx_get_shift_ms); the host route: wall ms",
+        "commit_parent": commit,
+        "libkfx_sha256": hashlib.sha256(open(kfx.LIB_PATH, "rb").read()).hexdigest(),
+        "copy_rate_TBps": COPY_TBS,
+        "shifts": rec,
+        "host_route_download_upload": sorted(route, key=lambda x: x["total_ms"])[len(route) // 2],
+        "host_route_bytes": 2 * 8 * nvox,
+    }
+    text = json.dumps(out, indent=1)
+    print(text)
+    if len(sys.argv) > 1:
+        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
+        with open(sys.argv[1], "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
