@@ -8,12 +8,30 @@
  * cv::Affine3f).  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg may load it — as the checker, never as the product.
  *
- * PARITY STATUS: the reference cannot be built here (CUDA + OpenCV, MSVC-only,
- * SURVEY.md §8c) and ships no tests or golden vectors, so this oracle is
- * "parity unpinned" against the original CUDA binary.  It is pinned instead by
- * analytic known-answer tests (tests/test_oracle_kat.py) and by the reference's
- * only data artifact (doc/poses.txt, format only).  Deviations from the CUDA
- * original are the "D" decisions of SURVEY.md Appendix A, listed in DESIGN.md.
+ * PARITY STATUS: the reference as a whole cannot be built here (CUDA + OpenCV,
+ * MSVC-only), but its per-thread kernels can: `make ref`
+ * (oracle/Makefile) compiles its three .cu files for the host behind
+ * oracle/ref_shim/, each CUDA intrinsic mapped to its IEEE counterpart with
+ * contraction off (the table in ref_shim/kfx_ref_shim.h; DESIGN.md's "div/sqrt"
+ * decision).
+ *   Pinned against the reference's own text under that mapping, bit for bit
+ *   over the project's case tables (tests/test_ref_parity.py), and against the
+ *   digests recorded from it (tests/golden/ref_digests.json, which also pin
+ *   libkfx: tests/test_gpu_ref_digests.py): kfo_integrate, kfo_raycast,
+ *   kfo_vertex_map, kfo_normal_map, kfo_resize_points_normals,
+ *   kfo_depth_truncation, kfo_render (bar the pixels where pow(float, int)
+ *   decides a byte, deviation `pow`), kfo_level_intrinsics, and
+ *   kfo_icp_accumulate's correspondence test and rows (the 27 sums rebuilt
+ *   from ICP::findCoresp's rows).
+ *   Still pinned by analytic known-answer tests alone
+ *   (tests/test_oracle_kat.py): kfo_pyr_down and kfo_bilateral (OpenCV's, not
+ *   in the reference tree); the ICP reduction order, kfo_icp_update's solve
+ *   and Rodrigues step (deliberate D deviations; icp_registration.cpp needs
+ *   OpenCV); kfo_extract_points (FullScan6 is warp-synchronous: it needs a
+ *   lock-step warp emulator, not a per-thread loop); the pipeline glue of
+ *   kinectfusion.cpp; and the pose text format (doc/poses.txt).
+ * Deviations from the CUDA original are the "D" decisions of SURVEY.md
+ * Appendix A, listed in DESIGN.md.
  *
  * Single-threaded, built with -ffp-contract=off (oracle/Makefile) so every float
  * operation happens in the written order with IEEE rounding.

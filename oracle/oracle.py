@@ -2,8 +2,13 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import
 this module, and only as the checker.  The product (libkfx.so) never links or
-calls it.  Parity status: unpinned against the CUDA original (see
-kfx_oracle.h); pinned by analytic KATs in tests/test_oracle_kat.py.
+calls it.  Parity status (see kfx_oracle.h): integrate, raycast, the vertex /
+normal / resize / render kernels, the level intrinsics and the ICP
+correspondence rows are pinned against the reference's own kernels compiled
+for the host (build_ref / ref_lib below, tests/test_ref_parity.py) and against
+their recorded digests (tests/golden/ref_digests.json); pyrDown, the bilateral
+filter, the ICP reduction order, solve and Rodrigues step and FullScan6 stay
+pinned by the analytic KATs of tests/test_oracle_kat.py alone.
 """
 from __future__ import annotations
 
@@ -20,7 +25,54 @@ sys.path.insert(0, os.path.join(_ROOT, "slam-kinectfusion_amd"))
 from kfx.abi import (Intrinsics, Params, Pose, fptr, i16ptr, i32ptr, i64ptr, u8ptr)  # noqa: E402
 
 LIB_PATH = os.path.join(_HERE, "build", "libkfx_oracle.so")
+REF_LIB_PATH = os.path.join(_HERE, "_ref", "libkfx_ref.so")
 _lib = None
+_ref = False  # False: not looked for yet; None: not available
+
+
+def ref_source() -> str | None:
+    """The reference checkout `make ref` reads (the Makefile's REF), or None when it is not there."""
+    r = subprocess.run(["make", "-s", "-C", _HERE, "ref-path"], capture_output=True, text=True)
+    path = r.stdout.strip()
+    return path if r.returncode == 0 and os.path.isdir(os.path.join(path, "kfusion", "src")) else None
+
+
+def build_ref() -> str | None:
+    """Compile the reference's per-thread kernels for the host (oracle/Makefile,
+    target `ref`) where the reference is present; None, silently, where it is not."""
+    if ref_source() is None:
+        return None
+    subprocess.run(["make", "-s", "-C", _HERE, "ref"], check=True)
+    return REF_LIB_PATH
+
+
+def ref_lib():
+    """ctypes binding of libkfx_ref.so (ref_driver.cpp): rebuilt when the
+    reference is present, loaded as it stands when only the library is, None
+    when neither is."""
+    global _ref
+    if _ref is False:
+        if build_ref() is None and not os.path.exists(REF_LIB_PATH):
+            _ref = None
+            return None
+        L = C.CDLL(REF_LIB_PATH)
+        v, f, i = C.c_void_p, C.c_float, C.c_int
+        L.ref_voxel_bytes.restype = i
+        L.ref_integrate.argtypes = [v, v, v, f, v, v, v, v, i, i, v]
+        L.ref_raycast.argtypes = [v, v, v, v, v, v, v, v, v, i, i]
+        L.ref_depth_truncation.argtypes = [v, i, i, f]
+        L.ref_vertex_map.argtypes = [v, i, i, v, v]
+        L.ref_normal_map.argtypes = [v, i, i, v]
+        L.ref_resize.argtypes = [v, v, i, i, v, v]
+        L.ref_render.argtypes = [v, v, i, i, v, i, v]
+        L.ref_level_intrinsics.argtypes = [v, v, i, v, v]
+        L.ref_icp_rows.argtypes = [v, v, v, v, i, i, v, v, v, f, f, v]
+        for name in ("ref_integrate", "ref_raycast", "ref_depth_truncation", "ref_vertex_map", "ref_normal_map",
+                     "ref_resize", "ref_render", "ref_level_intrinsics", "ref_icp_rows"):
+            getattr(L, name).restype = None
+        assert L.ref_voxel_bytes() == 8
+        _ref = L
+    return _ref
 
 
 def build() -> str:

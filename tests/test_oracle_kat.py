@@ -1,7 +1,12 @@
 """Known-answer tests that pin the CPU oracle (oracle/kfx_oracle.cpp).
 
-The reference ships no tests or golden vectors and cannot be built here
-(SURVEY.md §8c), so the oracle is pinned by:
+The reference ships no tests or golden vectors.  Its per-thread kernels are
+compiled for the host and compared with the oracle bit for bit in
+test_ref_parity.py (integrate, raycast, vertex / normal / resize / render
+kernels, level intrinsics, the ICP correspondence rows).  What that build
+cannot reach stays pinned here alone: pyrDown and the bilateral filter
+(OpenCV's), the ICP solve and Rodrigues step, FullScan6 (warp-synchronous),
+the pipeline glue and the pose text.  The KATs pin all of the oracle by:
   * closed-form answers (planes, identical frames, constants);
   * an independent vectorised numpy restatement of the OpenCV pieces;
   * tracking against the analytic ground truth of the synthetic scene;
