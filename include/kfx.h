@@ -223,6 +223,24 @@ int kfx_debug_int_tiles(kfx_ctx *ctx, int on);
 #define KFX_ICP_PLAN_WORDS 16
 int kfx_debug_get_icp_sums(kfx_ctx *ctx, int64_t out[27]);
 int kfx_debug_cap_icp_blocks(kfx_ctx *ctx, int cap, int32_t plan[KFX_ICP_PLAN_WORDS]);
+/* Debug hooks of the extraction (added under ABI version 2,
+ * nothing else changed).  The extraction sweeps (count, emit and pool pass of
+ * kfx_extract_points / kfx_extract_mesh and their _attr forms) give every wave
+ * K consecutive units (column tile x 8-slice chunk) of one chunk; K is 1 below
+ * 131072 units and grows to 64 with the volume.  kfx_debug_extract_units:
+ * units in {1, 2, 4, 8, 16, 32, 64} forces that K in every sweep of this
+ * context, so a small volume takes the paths of a large one; 0 restores the
+ * automatic rule; anything else returns KFX_ERR_ARG and changes nothing.
+ * Returns the K the next extraction of this context's whole (or slab's) volume
+ * uses.  Results are identical for every K.
+ * kfx_debug_scan: the exclusive scan the extraction and the eviction turn
+ * their per-unit counts into offsets with, on its own: uploads counts[n], runs
+ * the scan on the context's stream with the extraction's workspaces and
+ * downloads offsets[n] (offsets[i] = counts[0] + ... + counts[i-1], 64-bit)
+ * and *total (the sum of all counts).  KFX_ERR_ARG on a null pointer, n < 1 or
+ * n > 2^28. */
+int kfx_debug_extract_units(kfx_ctx *ctx, int units);
+int kfx_debug_scan(kfx_ctx *ctx, const uint32_t *counts, int64_t n, uint64_t *offsets, uint64_t *total);
 /* Measurement hook (tools/slab_record.py): device time of the sharded ICP's
  * per-rank launches for band `rank` of `world` (kfx_set_icp_allreduce's
  * k_icp_acc over the band's rows of every level + the k_icp_solve, 19

@@ -1800,6 +1800,44 @@ int kfx_debug_cap_icp_blocks(kfx_ctx *c, int cap, int32_t plan[KFX_ICP_PLAN_WORD
   return c->icp_persistent ? 1 : 0;
 }
 
+int kfx_debug_extract_units(kfx_ctx *c, int units) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (units < 0 || units > 64 || (units & (units - 1))) return set_err(KFX_ERR_ARG, "units per wave: 0 or a power of two up to 64");
+  c->vol.xunits = units;
+  // the slices extract_items sweeps
+  return xsweep_units(c->vol, std::max(0, c->vol.own0), std::min(c->vol.own1, c->vol.Z - 1));
+}
+
+int kfx_debug_scan(kfx_ctx *c, const uint32_t *counts, int64_t n, uint64_t *offsets, uint64_t *total) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!counts || !offsets || !total) return set_err(KFX_ERR_ARG, "null argument");
+  if (n < 1 || n > (int64_t)1 << 28) return set_err(KFX_ERR_ARG, "n outside 1 .. 2^28");
+  HIPCHK(hipStreamSynchronize(c->stream));
+  // the workspace of extract_items' two-pass path: counts | offsets | block sums | total
+  const size_t un = (size_t)n, nb = scan_blocks(un);
+  char *ws = nullptr;
+  HIPCHK(hipMalloc(&ws, un * 4 + un * 8 + nb * 8 + 64));
+  unsigned *dc = (unsigned *)ws;
+  unsigned long long *doff = (unsigned long long *)(ws + ((un * 4 + 7) & ~(size_t)7));
+  unsigned long long *bsum = doff + un;
+  unsigned long long *dtot = bsum + nb;
+  unsigned long long ht = 0;
+  hipError_t e = hipMemcpyAsync(dc, counts, un * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    launch_scan(c->stream, dc, doff, bsum, un, dtot);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(offsets, doff, un * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(ws);
+  if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("debug_scan: ") + hipGetErrorString(e));
+  *total = ht;
+  return KFX_OK;
+}
+
 int kfx_set_icp_allreduce(kfx_ctx *c, int enabled) {
   if (!c) return set_err(KFX_ERR_ARG, "null context");
   if (!c->slab) return set_err(KFX_ERR_STATE, "ICP partial all-reduce needs a slab context");

@@ -394,6 +394,14 @@ static int extract_chunks(int zlo, int zhi) {
 size_t extract_waves(const VolView &v, int zlo, int zhi) {
   return (size_t)v.tiles_x * v.tiles_y * (size_t)extract_chunks(zlo, zhi);
 }
+int xsweep_units(const VolView &v, int zlo, int zhi) {
+  if (v.xunits) return v.xunits;  // kfx_debug_extract_units
+  // units per wave: as many as keep >= 64 K waves (at least 1, at most 64)
+  const size_t units = extract_waves(v, zlo, zhi);
+  int K = 1;
+  while (K < 64 && units / (size_t)(2 * K) >= (size_t)KFX_XSWEEP_WAVES) K *= 2;
+  return K;
+}
 template <int kMode, bool kAttr = false>
 static void launch_xsweep(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
                           unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap,
@@ -401,10 +409,7 @@ static void launch_xsweep(hipStream_t s, const VolView &v, DevPose vpose, int zl
   const int nc = extract_chunks(zlo, zhi);
   if (nc == 0) return;
   const int tiles = v.tiles_x * v.tiles_y;
-  // units per wave: as many as keep >= 64 K waves (at least 1, at most 64)
-  const size_t units = (size_t)tiles * nc;
-  int K = 1;
-  while (K < 64 && units / (size_t)(2 * K) >= (size_t)KFX_XSWEEP_WAVES) K *= 2;
+  const int K = xsweep_units(v, zlo, zhi);
   dim3 grd((tiles + 4 * K - 1) / (4 * K), nc);  // 4 waves of K units per block
   if (tab)
     hipLaunchKernelGGL((k_xsweep<kMode, true, kAttr>), grd, dim3(256), 0, s, v, vpose, zlo, zhi, tab, counts, offsets,

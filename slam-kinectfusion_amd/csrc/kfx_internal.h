@@ -174,6 +174,7 @@ struct VolView {
   int inchunk;
   int iadapt;  // length-capped chunks + longest-first order (deep volumes), else geometric chunks
   int force64;  // kfx_debug_force_index64: integrate / raycast take the 64-bit-index kernels at any size
+  int xunits;   // kfx_debug_extract_units: units per wave of every extraction sweep (0: xsweep_units' own rule)
   unsigned *rdur;  // raycast: each wave's duration in the last frame (1024-cycle units; issue priority hint)
   // Integrate's per-frame tile table (k_int_tiles): what a
   // (tile, chunk) wave's prologue used to compute, written once per tile
@@ -366,6 +367,9 @@ void launch_slice_work(hipStream_t s, const VolView &v, DevPose vol2cam, LevelGe
 // attr (here and below): attributed items of 7 32-bit words per vertex
 // (kfx_vertex: position, normal, colour) in place of float3 vertices
 size_t extract_waves(const VolView &v, int zlo, int zhi);
+// units (tile x 8-slice chunk) each wave of the sweeps below handles over [zlo, zhi): v.xunits, or
+// where that is 0 the rule that keeps enough waves (a power of two, 1..64); results do not depend on it
+int xsweep_units(const VolView &v, int zlo, int zhi);
 void launch_extract(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi,
                     unsigned *counts, const unsigned long long *offsets, float *out,
                     unsigned long long cap, bool attr = false);

@@ -43,7 +43,7 @@ EXPORTS = [
     "kfx_shift_volume", "kfx_evict_points", "kfx_get_volume_origin", "kfx_get_volume_pose", "kfx_get_shift_ms",
     "kfx_shift_for_pose",
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
-    "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks",
+    "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks", "kfx_debug_extract_units", "kfx_debug_scan",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
 ]
@@ -98,6 +98,8 @@ def lib():
         "kfx_debug_icp_band_ms": ([vp, i, i, i, P(C.c_float)], i),
         "kfx_debug_get_icp_sums": ([vp, P(C.c_int64)], i),
         "kfx_debug_cap_icp_blocks": ([vp, i, P(C.c_int32)], i),
+        "kfx_debug_extract_units": ([vp, i], i),
+        "kfx_debug_scan": ([vp, P(C.c_uint32), C.c_int64, P(C.c_uint64), P(C.c_uint64)], i),
         "kfx_get_icp_trace": ([vp, P(C.c_uint64), i], i),
         "kfx_get_cur_camera_pose": ([vp, P(Pose)], i),
         "kfx_get_frame_count": ([vp, P(i)], i),
@@ -580,6 +582,23 @@ class KinectFusion:
     def debug_icp_plan(self) -> dict:
         """The persistent ICP's plan in effect (debug_cap_icp_blocks without a change)."""
         return self.debug_cap_icp_blocks(-1)
+
+    def debug_extract_units(self, units: int = 0) -> int:
+        """Force `units` (1, 2, 4, ..., 64) units per wave in every extraction sweep of this
+        context (0: the automatic rule); returns the figure the next extraction uses."""
+        r = lib().kfx_debug_extract_units(self._h, int(units))
+        _check(min(r, 0), "kfx_debug_extract_units")
+        return r
+
+    def debug_scan(self, counts: np.ndarray):
+        """The extraction's exclusive offset scan of uint32 counts on the device:
+        ((n,) uint64 offsets, total)."""
+        cnt = np.ascontiguousarray(counts, np.uint32)
+        off = np.empty(len(cnt), np.uint64)
+        tot = C.c_uint64()
+        _check(lib().kfx_debug_scan(self._h, cnt.ctypes.data_as(C.POINTER(C.c_uint32)), len(cnt),
+                                    off.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(tot)), "kfx_debug_scan")
+        return off, int(tot.value)
 
     def debug_icp_band_ms(self, rank, world, reps=5) -> float:
         """Device ms of the sharded ICP's launches for band rank of world (no

@@ -51,11 +51,13 @@ def new_kf(dims=(64, 64, 64)):
 def shift_table(dims):
     X, Y, Z = dims
     one = [tuple(sg * m if k == a else 0 for k in range(3)) for a in range(3) for m in (8, 16) for sg in (1, -1)]
-    return one + [(8, -16, 24), (-8, -8, -8), (X, 0, 0), (0, -Y, 0), (0, 0, Z + 8), (-X - 16, 8, 0), (0, 0, 0)]
+    # a depth that is no multiple of 8: along z, shifts that leave part of a brick group (the +-8 above too)
+    part = [(0, 0, 40), (0, 0, -40), (8, 0, -40)] if Z % 8 else []
+    return one + part + [(8, -16, 24), (-8, -8, -8), (X, 0, 0), (0, -Y, 0), (0, 0, (Z + 7) // 8 * 8 + 8), (-X - 16, 8, 0), (0, 0, 0)]
 
 
 @pytest.mark.parametrize("force64", [False, True])
-@pytest.mark.parametrize("dims", [(64, 64, 64), (128, 64, 32)])
+@pytest.mark.parametrize("dims", [(64, 64, 64), (128, 64, 32), (64, 40, 44)])
 def test_contents(dims, force64):
     p = SC.params(dims)
     t, w, c = IC.random_volume(dims)
@@ -236,6 +238,32 @@ def test_eviction():
             assert sp.process(bgr[k], dep[k]) == KFX_OK
         assert kf.pipeline(bgr[4], dep[4]) == KFX_OK
         assert_same(kf, sp, "the frame after the evictions")
+
+
+def test_eviction_short_last_group():
+    """Z = 44: the last brick group holds 4 slices.  A shift towards the top drops part of it and
+    the group below; one away from the bottom leaves it alone."""
+    import extract_cases as EC
+    dims = (32, 24, 44)
+    p = SC.params(dims)
+    t, w, rgb = EC.dense(dims)
+    vol = O.Volume(dims, [float(r) for r in p.volu_range])
+    vol.tsdf[:], vol.weight[:] = t, w
+    vol.rgb.reshape(-1, 4)[:, :3] = rgb
+    vpose = SC.volume_pose(p, (0, 0, 0))
+    with new_kf(dims) as kf:
+        kf.upload_tsdf(EC.records(t, w, rgb))
+        full = kf.extract_points_attr()
+        ofull, n = O.extract_points(vol, vpose)
+        assert len(full) == n and np.array_equal(full["xyz"].view(np.uint32), ofull.view(np.uint32))
+        for s in ((0, 0, -8), (0, 0, 16)):
+            mask = SC.evicted_mask(vol, vpose, s)
+            ev = kf.evict_points(s)
+            assert len(ev) == mask.sum() and ev.tobytes() == full[mask].tobytes(), s
+            assert 0 < len(ev) < len(full)
+            assert kf.evict_count(s) == len(ev)
+            half = kf.evict_points(s, cap=len(ev) // 2)
+            assert half.tobytes() == ev[:len(ev) // 2].tobytes()
 
 
 # ---- 7. reset -------------------------------------------------------------------
