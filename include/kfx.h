@@ -531,6 +531,80 @@ int kfx_get_shift_ms(kfx_ctx *ctx, float out_ms[2]);      /* device ms of the la
 int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *volume_pose, const kfx_pose *cam_pose,
                        float ahead_m, int shift[3]);      /* host only, no context */
 
+/* ---- moving volume: bricks out and back in -----------------
+ * Added under ABI version 2, nothing else changed.  kfx_shift_volume is lossy:
+ * what leaves the window survives only as kfx_evict_points' surface points.
+ * These calls hand out the TSDF itself, brick by brick, and take it back when
+ * the window returns.
+ *
+ * A brick is 8 x 8 x 8 voxels: one 8x8 column tile x 8 slices, c = its index in
+ * the window per axis.  b is its world coordinate, b_k = origin_k / 8 + c_k
+ * (origin = kfx_get_volume_origin, a multiple of 8), which no shift changes.
+ *
+ * kfx_evict_bricks: the bricks kfx_shift_volume(shift) would drop (those with a
+ * voxel that is not kept) and that are not empty, ascending (b[2], b[1], b[0]).
+ * A brick is empty when all its stored bytes are 0: tsdf, weight and colour, as
+ * in a reset's voxels.  Writes min(cap, total) bricks, *n = total; cap = 0
+ * counts only.  Slices of a short last group (Z no multiple of 8) past Z are 0
+ * in the record.  The volume is unchanged; a zero shift gives 0 bricks; a
+ * component with |s| >= its dimension drops every brick.  Argument checks,
+ * stream ordering and blocking as kfx_evict_points (KFX_ERR_STATE on a slab of
+ * a world larger than 1).
+ *
+ * kfx_restore_bricks: every input brick whose world coordinate lies in the
+ * current window is written whole over the brick at c = b - origin / 8 (slices
+ * past Z are ignored); the others are skipped.  *n_restored (may be NULL) = the
+ * number written.  KFX_ERR_ARG, nothing written: a null `in` with n > 0, n < 0,
+ * a reserved field that is not 0, two input bricks with the same coordinate
+ * inside the window.  KFX_ERR_STATE as above.  The call runs on the context's
+ * stream behind every queued frame (staged and overlapped ones included) and in
+ * front of every later one, as kfx_shift_volume.  Pose, origin, previous-frame
+ * maps, pose record, frame count and a pending tracking status are untouched;
+ * captured graphs are kept (they hold neither contents nor maps).  Afterwards
+ * the context behaves as after kfx_upload_tsdf of the resulting records: the
+ * occupancy maps gain the marks of every restored brick's negative slices
+ * (they are supersets: bits of an overwritten brick may stay), every settled
+ * byte is cleared and integrate's gate is opened.  n = 0, or no brick in the
+ * window, does no device work and leaves the settled bytes alone.
+ *
+ * kfx_get_stream_ms: device ms of the last kfx_evict_bricks (count + scan +
+ * emit, without the copy to the host) and the last kfx_restore_bricks (memsets
+ * + launch, without the upload), from HIP events. */
+typedef struct kfx_brick {
+  int32_t b[3];        /* world brick coordinate: b_k = origin_k / 8 + c_k (c = brick index in the window) */
+  int32_t reserved;    /* 0 */
+  int16_t tsdf[512];   /* index 64*dz + 8*dy + dx: the device order of a brick */
+  uint8_t weight[512];
+  uint8_t rgb[512][4]; /* c0, c1, c2, 0 */
+} kfx_brick;           /* 3600 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(kfx_brick) == 3600, "kfx_brick is 3600 bytes");
+#else
+_Static_assert(sizeof(kfx_brick) == 3600, "kfx_brick is 3600 bytes");
+#endif
+int kfx_evict_bricks(kfx_ctx *ctx, const int shift[3], kfx_brick *out, int64_t cap, int64_t *n);
+int kfx_restore_bricks(kfx_ctx *ctx, const kfx_brick *in, int64_t n, int64_t *n_restored);
+int kfx_get_stream_ms(kfx_ctx *ctx, float out_ms[2]);     /* device ms of the last evict_bricks, last restore_bricks */
+
+/* Host-only brick store (no context, no GPU): where a caller keeps what is
+ * outside the window, keyed by world brick coordinate.
+ * kfx_brick_store_put: copies n bricks in; a coordinate already held is
+ * replaced (the later of two equal coordinates in one call wins).  KFX_ERR_ARG:
+ * a null store, n < 0, a null `in` with n > 0.
+ * kfx_brick_store_take_window: removes and returns the bricks with
+ * origin_k / 8 <= b_k < origin_k / 8 + ceil(dims_k / 8), ascending (b[2], b[1],
+ * b[0]); *n = how many there are; if cap < *n nothing is removed or written
+ * (size the buffer and call again).  KFX_ERR_ARG: a null store, origin, dims or
+ * n, an origin component that is no multiple of 8, a dims component below 1,
+ * cap < 0, a null `out` with cap > 0. */
+typedef struct kfx_brick_store kfx_brick_store;
+int kfx_brick_store_create(kfx_brick_store **out);
+int kfx_brick_store_destroy(kfx_brick_store *s);
+int kfx_brick_store_put(kfx_brick_store *s, const kfx_brick *in, int64_t n);
+int kfx_brick_store_count(const kfx_brick_store *s, int64_t *n);
+int kfx_brick_store_take_window(kfx_brick_store *s, const int origin[3], const int dims[3],
+                                kfx_brick *out, int64_t cap, int64_t *n);
+
 /* ---- dataset front-end (host only; no GPU needed) --------------------------
  * depth_sensor in its DATASET build (depth_sensor.cpp:11-46 open, :186-196
  * getFrame) without OpenCV: the PNG files of `<dir>/color` and `<dir>/depth` in

@@ -244,6 +244,10 @@ struct kfx_ctx {
   int origin[3] = {0, 0, 0};
   hipEvent_t ev_shift[4]{};
   bool shift_timed[2] = {false, false};
+  // bricks out and back in: the events around the last
+  // kfx_evict_bricks [0, 1] and the last kfx_restore_bricks [2, 3]
+  hipEvent_t ev_stream[4]{};
+  bool stream_timed[2] = {false, false};
   uint8_t *mc_tab = nullptr;      // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded
@@ -1329,6 +1333,8 @@ int kfx_destroy(kfx_ctx *c) {
   for (hipEvent_t e : c->ev_view)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_shift)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_stream)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -3334,6 +3340,121 @@ int kfx_get_shift_ms(kfx_ctx *c, float out_ms[2]) {
     if (!c->shift_timed[k]) continue;
     HIPCHK(hipEventSynchronize(c->ev_shift[2 * k + 1]));
     HIPCHK(hipEventElapsedTime(&out_ms[k], c->ev_shift[2 * k], c->ev_shift[2 * k + 1]));
+  }
+  return KFX_OK;
+}
+
+// ---- bricks out and back in ---------------------------------
+
+int kfx_evict_bricks(kfx_ctx *c, const int shift[3], kfx_brick *out, int64_t cap, int64_t *n) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = shift_args(c, shift))) return r;
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad brick buffer");
+  for (hipEvent_t &e : c->ev_stream)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const size_t units = brick_evict_units(c->vol, shift);
+  int64_t total = 0;
+  HIPCHK(hipEventRecord(c->ev_stream[0], c->stream));
+  if (units > 0) {
+    const size_t nb = scan_blocks(units);
+    char *ws = nullptr;
+    const size_t o_off = (units * 4 + 7) & ~(size_t)7;
+    HIPCHK(hipMalloc(&ws, o_off + units * 8 + nb * 8 + 64));
+    unsigned *counts = (unsigned *)ws;
+    unsigned long long *offsets = (unsigned long long *)(ws + o_off);
+    unsigned long long *bsum = offsets + units;
+    unsigned long long *dtot = bsum + nb;
+    launch_brick_count(c->stream, c->vol, shift, counts);
+    launch_scan(c->stream, counts, offsets, bsum, units, dtot);
+    unsigned long long ht = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    total = (int64_t)ht;
+    const int64_t m = std::min<int64_t>(total, cap);
+    void *dout = nullptr;
+    if (e == hipSuccess && m > 0) {
+      e = hipMalloc(&dout, (size_t)m * sizeof(kfx_brick));
+      if (e == hipSuccess) {
+        launch_brick_emit(c->stream, c->vol, shift, c->origin, counts, offsets, dout, (unsigned long long)m);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(c->ev_stream[1], c->stream);
+        if (e == hipSuccess)
+          e = hipMemcpyAsync(out, dout, (size_t)m * sizeof(kfx_brick), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(dout);
+      }
+    } else if (e == hipSuccess) {
+      e = hipEventRecord(c->ev_stream[1], c->stream);
+    }
+    (void)hipFree(ws);
+    if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("evict_bricks: ") + hipGetErrorString(e));
+  } else {
+    HIPCHK(hipEventRecord(c->ev_stream[1], c->stream));
+  }
+  c->stream_timed[0] = true;
+  if (n) *n = total;
+  return KFX_OK;
+}
+
+int kfx_restore_bricks(kfx_ctx *c, const kfx_brick *in, int64_t n, int64_t *n_restored) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (n < 0 || (n > 0 && !in)) return set_err(KFX_ERR_ARG, "bad brick list");
+  if (c->slab && c->world > 1)
+    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
+  // the host knows the origin: the bricks that land, and no two on one brick
+  const int64_t nb[3] = {c->vol.tiles_x, c->vol.tiles_y, (c->vol.Z + 7) / 8};
+  std::vector<uint64_t> cells;
+  for (int64_t i = 0; i < n; ++i) {
+    if (in[i].reserved != 0) return set_err(KFX_ERR_ARG, "restore_bricks: a reserved field that is not 0");
+    int64_t q[3];
+    bool inside = true;
+    for (int k = 0; k < 3; ++k) {
+      q[k] = (int64_t)in[i].b[k] - c->origin[k] / 8;
+      inside = inside && q[k] >= 0 && q[k] < nb[k];
+    }
+    if (inside) cells.push_back((uint64_t)((q[2] * nb[1] + q[1]) * nb[0] + q[0]));
+  }
+  std::sort(cells.begin(), cells.end());
+  if (std::adjacent_find(cells.begin(), cells.end()) != cells.end())
+    return set_err(KFX_ERR_ARG, "restore_bricks: two bricks with the same coordinate inside the window");
+  if (n_restored) *n_restored = (int64_t)cells.size();
+  if (cells.empty()) return KFX_OK;  // no device work; the settled bytes stay
+  for (hipEvent_t &e : c->ev_stream)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  // behind every queued frame, as the shift; the captured graphs hold neither
+  // the volume's contents nor its maps and stay
+  HIPCHK(hipStreamSynchronize(c->pstream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  void *din = nullptr;
+  if (hipMalloc(&din, (size_t)n * sizeof(kfx_brick)) != hipSuccess)
+    return set_err(KFX_ERR_OOM, "restore_bricks: hipMalloc(" + std::to_string((size_t)n * sizeof(kfx_brick)) + ")");
+  hipError_t e = hipMemcpyAsync(din, in, (size_t)n * sizeof(kfx_brick), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(c->ev_stream[2], c->stream);
+  if (e == hipSuccess) {
+    launch_brick_restore(c->stream, c->vol, c->origin, din, (size_t)n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev_stream[3], c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(din);
+  if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("restore_bricks: ") + hipGetErrorString(e));
+  c->stream_timed[1] = true;
+  return KFX_OK;
+}
+
+int kfx_get_stream_ms(kfx_ctx *c, float out_ms[2]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  for (int k = 0; k < 2; ++k) {
+    out_ms[k] = 0.f;
+    if (!c->stream_timed[k]) continue;
+    HIPCHK(hipEventSynchronize(c->ev_stream[2 * k + 1]));
+    HIPCHK(hipEventElapsedTime(&out_ms[k], c->ev_stream[2 * k], c->ev_stream[2 * k + 1]));
   }
   return KFX_OK;
 }

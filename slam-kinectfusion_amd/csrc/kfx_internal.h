@@ -416,6 +416,21 @@ size_t evict_units(const VolView &v, const int shift[3]);
 // writes them at offsets (< cap)
 void launch_evict(hipStream_t s, const VolView &v, DevPose vpose, const int shift[3], unsigned *counts,
                   const unsigned long long *offsets, float *out, unsigned long long cap);
+// bricks out and back in.  A unit is a brick with a voxel the
+// shift drops, numbered ascending (z group, tile row, tile); origin: the
+// window's voxel origin (multiples of 8); records are kfx_brick (3600 bytes,
+// 16-byte aligned).
+size_t brick_evict_units(const VolView &v, const int shift[3]);
+// counts[unit] = 1 iff some stored byte of the brick is not 0
+void launch_brick_count(hipStream_t s, const VolView &v, const int shift[3], unsigned *counts);
+// record offsets[unit] (< cap) = the unit's brick, for every unit with counts[unit] != 0
+void launch_brick_emit(hipStream_t s, const VolView &v, const int shift[3], const int origin[3],
+                       const unsigned *counts, const unsigned long long *offsets, void *out,
+                       unsigned long long cap);
+// the records `in` whose coordinate lies in the window, written over their
+// bricks (no two for one brick); the occupancy maps gain their marks, every
+// settled byte is cleared and the gate opened
+void launch_brick_restore(hipStream_t s, const VolView &v, const int origin[3], const void *in, size_t n);
 
 // ---- kfx_volume_io.hip ----------------------------------------------------
 void launch_export_records(hipStream_t s, VolView v, int z0, int nz, uint64_t *dst);

@@ -1,6 +1,7 @@
 // kfx_shift.hip — the moving volume: the in-place shift of the
-// TSDF window by whole bricks, and the extraction of the surface points the
-// shift would drop (eviction).  Compiled like kfx_extract.hip
+// TSDF window by whole bricks, the extraction of the surface points the
+// shift would drop (eviction), and the bricks themselves handed out and taken
+// back.  Compiled like kfx_extract.hip
 // (-ffp-contract=off), whose per-voxel functions the eviction shares
 // (kfx_extract_dev.h), so an evicted item has kfx_extract_points_attr's bytes.
 #include <algorithm>
@@ -227,6 +228,137 @@ __global__ __launch_bounds__(256) void k_evict(VolView v, DevPose aff, BrickRegi
   if (!kEmit && lane == 0) counts[un] = total;
 }
 
+// ---------------------------------------------------------------------------
+// Bricks out and back in.  A kfx_brick record is 225 pieces of
+// 16 bytes: the header {b0, b1, b2, 0}, then the brick's three runs as the
+// volume stores them, 64 pieces of tsdf, 32 of weight, 128 of colour (k_shift's
+// thread order).  The records lie in hipMalloc'ed buffers, 3600 = 225 * 16
+// bytes apart, so every access is a 16-byte vector access.
+constexpr int kBrickPieces = 225;
+
+struct BrickOrigin {
+  int o[3];  // the window's origin in bricks
+};
+
+// The bricks with a voxel the shift drops, one slab per axis.  Where every
+// dimension is a multiple of 8 this is make_region(v, s, 0); a short last group
+// (8 nb > dim) makes the slab at the high face start one brick earlier: voxel x
+// leaves iff x >= dim + s, so the first brick with such a voxel is (dim + s) / 8.
+BrickRegion make_drop_region(const VolView &v, const int s[3]) {
+  BrickRegion rg = make_region(v, s, 0);
+  const int dims[3] = {v.X, v.Y, v.Z};
+  for (int k = 0; k < 3; ++k)
+    if (s[k] < 0) rg.a[k] = dims[k] + s[k] <= 0 ? 0 : (dims[k] + s[k]) / 8;
+  rg.nX = rg.b[0] - rg.a[0];
+  const unsigned long long nY = (unsigned long long)(rg.b[1] - rg.a[1]);
+  rg.P = nY * v.tiles_x + ((unsigned long long)v.tiles_y - nY) * rg.nX;
+  const unsigned long long nZ = (unsigned long long)(rg.b[2] - rg.a[2]);
+  rg.total = nZ * rg.T + ((unsigned long long)((v.Z + 7) / 8) - nZ) * rg.P;
+  return rg;
+}
+
+__device__ __forceinline__ bool nonzero(const uint4 &r) { return (r.x | r.y | r.z | r.w) != 0u; }
+
+// Count: one wave per cell of the region, counts[cell] = 1 iff some stored byte
+// of the brick is not 0.  The 512 B of weight first (a brick that was ever
+// integrated shows there), the tsdf and the colour only while all is 0.
+template <typename I>
+__global__ __launch_bounds__(256) void k_brick_count(VolView v, BrickRegion rg, unsigned *counts) {
+  const unsigned long long un = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (un >= rg.total) return;  // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  int cz = 0, tile = 0;
+  region_cell(v, rg, un, &cz, &tile);
+  const int nsl = min(8, v.zn - 8 * cz);                // slices the group holds (a last group may be short)
+  const I col = (I)tile * (I)v.zn + (I)(8 * cz);        // slices stored in front of the brick
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  uint4 r = zero;
+  if (lane < 4 * nsl) r = reinterpret_cast<const uint4 *>(v.weight)[col * (I)4 + (I)lane];
+  unsigned long long any = __ballot(nonzero(r));
+  if (!any) {
+    r = zero;
+    if (lane < 8 * nsl) r = reinterpret_cast<const uint4 *>(v.tsdf)[col * (I)8 + (I)lane];
+    any = __ballot(nonzero(r));
+  }
+  if (!any) {
+    uint4 q = zero;
+    r = zero;
+    if (lane < 16 * nsl) r = reinterpret_cast<const uint4 *>(v.rgb)[col * (I)16 + (I)lane];
+    if (lane + 64 < 16 * nsl) q = reinterpret_cast<const uint4 *>(v.rgb)[col * (I)16 + (I)(lane + 64)];
+    any = __ballot(nonzero(r) || nonzero(q));
+  }
+  if (lane == 0) counts[un] = any ? 1u : 0u;
+}
+
+// the thread's array (as 16-byte pieces), pieces per slice and piece of a
+// brick: k_shift's assignment of threads 0..223
+__device__ __forceinline__ uint4 *brick_piece(const VolView &v, int t, int *ps, int *u) {
+  if (t < 64) {
+    *ps = 8, *u = t;
+    return reinterpret_cast<uint4 *>(v.tsdf);
+  }
+  if (t < 96) {
+    *ps = 4, *u = t - 64;
+    return reinterpret_cast<uint4 *>(v.weight);
+  }
+  *ps = 16, *u = t - 96;
+  return reinterpret_cast<uint4 *>(v.rgb);
+}
+
+// Emit: one block per cell; the non-empty brick of rank offsets[cell] < cap is
+// written as record `rank`: thread t < 224 its piece (0 for a slice past the
+// volume's end), thread 224 the header.
+template <typename I>
+__global__ __launch_bounds__(256) void k_brick_emit(VolView v, BrickRegion rg, BrickOrigin ob, const unsigned *counts,
+                                                    const unsigned long long *offsets, uint4 *out,
+                                                    unsigned long long cap) {
+  const unsigned long long un = blockIdx.x;
+  if (!counts[un]) return;  // (block-uniform, as the next)
+  const unsigned long long at = offsets[un];
+  if (at >= cap) return;
+  int cz = 0, tile = 0;
+  region_cell(v, rg, un, &cz, &tile);
+  uint4 *rec = out + (size_t)at * kBrickPieces;
+  const int t = (int)threadIdx.x;
+  if (t < 224) {
+    int ps, u;
+    const uint4 *base = brick_piece(v, t, &ps, &u);
+    uint4 r = make_uint4(0u, 0u, 0u, 0u);
+    if (8 * cz + u / ps < v.zn) r = base[((I)tile * (I)v.zn + (I)(8 * cz)) * (I)ps + (I)u];
+    rec[1 + t] = r;
+  } else if (t == 224) {
+    rec[0] = make_uint4((unsigned)(ob.o[0] + tile % v.tiles_x), (unsigned)(ob.o[1] + tile / v.tiles_x),
+                        (unsigned)(ob.o[2] + cz), 0u);
+  }
+}
+
+// Restore: one block per input record.  A brick outside the window is skipped
+// (block-uniform); otherwise thread t < 224 stores its piece over the brick at
+// c = b - origin / 8 (the host has refused two records for one brick), and the
+// first wave, which holds the tsdf, marks the occupancy maps as k_shift does.
+template <typename I>
+__global__ __launch_bounds__(256) void k_brick_restore(VolView v, BrickOrigin ob, const uint4 *in) {
+  const uint4 *rec = in + (size_t)blockIdx.x * kBrickPieces;
+  const uint4 h = rec[0];
+  // (mod 2^32: |origin / 8| < 2^28, so a coordinate outside the window cannot wrap into it)
+  const unsigned cx = h.x - (unsigned)ob.o[0], cy = h.y - (unsigned)ob.o[1], cz = h.z - (unsigned)ob.o[2];
+  if (cx >= (unsigned)v.tiles_x || cy >= (unsigned)v.tiles_y || cz >= (unsigned)((v.zn + 7) >> 3)) return;
+  const int t = (int)threadIdx.x;
+  if (t >= 224) return;  // (no barrier below)
+  const int tile = (int)cy * v.tiles_x + (int)cx;
+  int ps, u;
+  uint4 *base = brick_piece(v, t, &ps, &u);
+  const int du = u / ps;
+  const bool stored = 8 * (int)cz + du < v.zn;  // a slice past the volume's end is ignored
+  const uint4 r = stored ? rec[1 + t] : make_uint4(0u, 0u, 0u, 0u);
+  if (stored) base[((I)tile * (I)v.zn + (I)(8 * (int)cz)) * (I)ps + (I)u] = r;
+  if (t < 64) {  // the brick's tsdf: slices with a negative value
+    const bool neg = ((r.x | r.y | r.z | r.w) & 0x80008000u) != 0u;
+    const int zq = v.zb + 8 * (int)cz + du;
+    if (__any(neg)) occ_mark_wave(v, tile, neg ? zq : INT_MAX, neg ? zq : -1, t);
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -275,6 +407,52 @@ void launch_evict(hipStream_t s, const VolView &v, DevPose vpose, const int shif
   else
     hipLaunchKernelGGL(k_evict<false>, grd, dim3(256), 0, s, v, vpose, rg, counts, offsets,
                        reinterpret_cast<uint32_t *>(out), cap);
+}
+
+static bool index64(const VolView &v) { return v.force64 || v.local_voxels() >= ((size_t)1 << 31); }
+static BrickOrigin brick_origin(const int origin[3]) { return {{origin[0] / 8, origin[1] / 8, origin[2] / 8}}; }
+
+size_t brick_evict_units(const VolView &v, const int shift[3]) { return (size_t)make_drop_region(v, shift).total; }
+
+void launch_brick_count(hipStream_t s, const VolView &v, const int shift[3], unsigned *counts) {
+  const BrickRegion rg = make_drop_region(v, shift);
+  if (rg.total == 0) return;
+  const dim3 grd((unsigned)((rg.total + 3) / 4));
+  if (index64(v))
+    hipLaunchKernelGGL((k_brick_count<unsigned long long>), grd, dim3(256), 0, s, v, rg, counts);
+  else
+    hipLaunchKernelGGL((k_brick_count<unsigned>), grd, dim3(256), 0, s, v, rg, counts);
+}
+
+void launch_brick_emit(hipStream_t s, const VolView &v, const int shift[3], const int origin[3],
+                       const unsigned *counts, const unsigned long long *offsets, void *out,
+                       unsigned long long cap) {
+  const BrickRegion rg = make_drop_region(v, shift);
+  if (rg.total == 0) return;
+  const dim3 grd((unsigned)rg.total);
+  if (index64(v))
+    hipLaunchKernelGGL((k_brick_emit<unsigned long long>), grd, dim3(256), 0, s, v, rg, brick_origin(origin), counts,
+                       offsets, static_cast<uint4 *>(out), cap);
+  else
+    hipLaunchKernelGGL((k_brick_emit<unsigned>), grd, dim3(256), 0, s, v, rg, brick_origin(origin), counts, offsets,
+                       static_cast<uint4 *>(out), cap);
+}
+
+void launch_brick_restore(hipStream_t s, const VolView &v, const int origin[3], const void *in, size_t n) {
+  if (n == 0) return;
+  // new contents under whatever byte was set: as the upload and the shift, no
+  // settled byte and the gate open; the occupancy maps only gain bits
+  if (v.settled) {
+    (void)hipMemsetAsync(v.settled, 0, v.settled_bytes(), s);
+    (void)hipMemsetAsync(v.sgate, 0x40, 4, s);
+  }
+  const dim3 grd((unsigned)n);
+  if (index64(v))
+    hipLaunchKernelGGL((k_brick_restore<unsigned long long>), grd, dim3(256), 0, s, v, brick_origin(origin),
+                       static_cast<const uint4 *>(in));
+  else
+    hipLaunchKernelGGL((k_brick_restore<unsigned>), grd, dim3(256), 0, s, v, brick_origin(origin),
+                       static_cast<const uint4 *>(in));
 }
 
 }  // namespace kfx

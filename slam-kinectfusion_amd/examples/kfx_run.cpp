@@ -6,9 +6,14 @@
 // fused colour rendered from the last tracked pose, kfx_render_view;
 // followed_cloud.ply makes the volume follow the camera, kfx_shift_for_pose /
 // kfx_evict_points / kfx_shift_volume after every frame, and holds the evicted
-// points followed by the final cloud).
+// points followed by the final cloud; a non-empty eighth argument makes the
+// follow loop lossless, DESIGN.md §21: the bricks a shift drops go into a host
+// brick store, kfx_evict_bricks / kfx_brick_store_put, and those of the new
+// window come back, kfx_brick_store_take_window / kfx_restore_bricks.  The
+// followed cloud keeps its meaning, the points evicted at each shift, then the
+// final window: a surface that left and returned appears once per departure).
 //   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
-//                  [followed_cloud.ply]
+//                  [followed_cloud.ply] [stream]
 #include <chrono>
 #include <cstdio>
 #include <vector>
@@ -19,7 +24,7 @@ int main(int argc, char **argv) {
   if (argc < 2) {
     std::fprintf(stderr,
                  "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm] "
-                 "[followed_cloud.ply]\n",
+                 "[followed_cloud.ply] [stream]\n",
                  argv[0]);
     return 2;
   }
@@ -51,6 +56,15 @@ int main(int argc, char **argv) {
   const float ahead = 0.5f + p.volu_range[2] / 2;
   std::vector<kfx_vertex> evicted;
   int shifts = 0;
+  // lossless follow: what a shift drops waits in the store until the window returns to it
+  const bool stream = argc > 8 && argv[8][0];
+  kfx_brick_store *store = nullptr;
+  std::vector<kfx_brick> bricks;
+  long long bricks_out = 0, bricks_in = 0;
+  if (stream && kfx_brick_store_create(&store) != KFX_OK) {
+    std::fprintf(stderr, "error: %s\n", kfx_last_error());
+    return 1;
+  }
   for (int k = 0; k < n; ++k) {
     if (kfx_dataset_read(ds, k, bgr.data(), depth.data()) != KFX_OK) {
       std::printf("no image! (%s)\n", kfx_last_error());
@@ -66,7 +80,7 @@ int main(int argc, char **argv) {
       return 1;
     }
     if (!follow) continue;
-    if (r == KFX_TRACKING_LOST) {  // the device reset cannot move the volume back: kfx.h
+    if (r == KFX_TRACKING_LOST) {  // the device reset cannot move the volume back: kfx.h (the store is kept)
       if (kfx_reset(ctx) != KFX_OK) {
         std::fprintf(stderr, "error: %s\n", kfx_last_error());
         return 1;
@@ -88,12 +102,45 @@ int main(int argc, char **argv) {
     }
     const size_t at = evicted.size();
     evicted.resize(at + (size_t)ne);
-    if ((ne > 0 && kfx_evict_points(ctx, s, evicted.data() + at, ne, &ne) != KFX_OK) ||
-        kfx_shift_volume(ctx, s) != KFX_OK) {
+    if (ne > 0 && kfx_evict_points(ctx, s, evicted.data() + at, ne, &ne) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    if (stream) {  // the bricks themselves, before they go
+      int64_t nb = 0;
+      if (kfx_evict_bricks(ctx, s, nullptr, 0, &nb) != KFX_OK) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      bricks.resize((size_t)nb);
+      if ((nb > 0 && kfx_evict_bricks(ctx, s, bricks.data(), nb, &nb) != KFX_OK) ||
+          kfx_brick_store_put(store, bricks.data(), nb) != KFX_OK) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      bricks_out += nb;
+    }
+    if (kfx_shift_volume(ctx, s) != KFX_OK) {
       std::fprintf(stderr, "error: %s\n", kfx_last_error());
       return 1;
     }
     ++shifts;
+    if (stream) {  // and those the new window holds, back in
+      int origin[3];
+      int64_t nb = 0, nr = 0;
+      if (kfx_get_volume_origin(ctx, origin) != KFX_OK ||
+          kfx_brick_store_take_window(store, origin, p.volu_dims, nullptr, 0, &nb) != KFX_OK) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      bricks.resize((size_t)nb);
+      if ((nb > 0 && kfx_brick_store_take_window(store, origin, p.volu_dims, bricks.data(), nb, &nb) != KFX_OK) ||
+          kfx_restore_bricks(ctx, bricks.data(), nb, &nr) != KFX_OK) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      bricks_in += nr;
+    }
   }
   int frames = 0;
   kfx_get_frame_count(ctx, &frames);
@@ -133,6 +180,12 @@ int main(int argc, char **argv) {
     }
     std::printf("followed: %d shifts, %lld evicted points, %lld in the volume\n", shifts, (long long)at,
                 (long long)nf);
+  }
+  if (stream) {
+    int64_t held = 0;
+    kfx_brick_store_count(store, &held);
+    std::printf("streamed: %lld bricks out, %lld back in, %lld held\n", bricks_out, bricks_in, (long long)held);
+    kfx_brick_store_destroy(store);
   }
   std::printf("end! %d frames, frame_count %d, %.3f ms/frame in kfx_pipeline (host frames, PCIe incl.)\n", n,
               frames, n ? 1e3 * gpu_s / n : 0.0);

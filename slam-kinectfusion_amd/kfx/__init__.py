@@ -20,7 +20,7 @@ from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, Intr
 
 __all__ = ["KinectFusion", "KfxError", "Dataset", "png_info", "png_read_bgr8", "png_read_depth", "parse_intr",
            "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "write_ply_attr", "write_ply_mesh_attr",
-           "write_ppm", "shift_for_pose", "VIEW_KINDS", "VERTEX_DTYPE", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
+           "write_ppm", "shift_for_pose", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
            "default_params", "KFX_FRAME_CUR", "KFX_FRAME_PREV", "KFX_OK", "KFX_TRACKING_LOST", "EXPORTS"]
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +42,8 @@ EXPORTS = [
     "kfx_render_view", "kfx_get_view_ms", "kfx_write_ppm",
     "kfx_shift_volume", "kfx_evict_points", "kfx_get_volume_origin", "kfx_get_volume_pose", "kfx_get_shift_ms",
     "kfx_shift_for_pose",
+    "kfx_evict_bricks", "kfx_restore_bricks", "kfx_get_stream_ms", "kfx_brick_store_create", "kfx_brick_store_destroy",
+    "kfx_brick_store_put", "kfx_brick_store_count", "kfx_brick_store_take_window",
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks", "kfx_debug_extract_units", "kfx_debug_scan",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
@@ -153,6 +155,14 @@ def lib():
         "kfx_get_volume_pose": ([vp, P(Pose)], i),
         "kfx_get_shift_ms": ([vp, P(f)], i),
         "kfx_shift_for_pose": ([P(Params), P(Pose), P(Pose), f, P(i)], i),
+        "kfx_evict_bricks": ([vp, P(i), vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_restore_bricks": ([vp, vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_get_stream_ms": ([vp, P(f)], i),
+        "kfx_brick_store_create": ([P(vp)], i),
+        "kfx_brick_store_destroy": ([vp], i),
+        "kfx_brick_store_put": ([vp, vp, C.c_int64], i),
+        "kfx_brick_store_count": ([vp, P(C.c_int64)], i),
+        "kfx_brick_store_take_window": ([vp, P(i), P(i), vp, C.c_int64, P(C.c_int64)], i),
         "kfx_volume_checksum": ([vp, P(C.c_uint64)], i),
         "kfx_write_ply": ([C.c_char_p, P(f), C.c_int64], i),
         "kfx_save_pointcloud": ([vp, C.c_char_p, C.c_int64], i),
@@ -321,6 +331,68 @@ class Dataset:
         if self._h:
             lib().kfx_dataset_close(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# kfx_brick (3600 bytes): the world brick coordinate and the brick's tsdf, weight and colour in
+# the device order of a brick, index 64*dz + 8*dy + dx
+BRICK_DTYPE = np.dtype([("b", "<i4", 3), ("reserved", "<i4"), ("tsdf", "<i2", 512), ("weight", "u1", 512),
+                        ("rgb", "u1", (512, 4))])
+assert BRICK_DTYPE.itemsize == 3600
+
+
+def _bricks(bricks) -> np.ndarray:
+    return np.ascontiguousarray(bricks, BRICK_DTYPE).ravel()
+
+
+class BrickStore:
+    """The host-only brick store (kfx_brick_store_*): bricks outside the window, keyed by their
+    world coordinate.  Needs the library, not a GPU."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        _check(lib().kfx_brick_store_create(C.byref(h)), "kfx_brick_store_create")
+        self._h = h
+
+    def put(self, bricks):
+        """Copy (N,) BRICK_DTYPE bricks in; a coordinate already held is replaced."""
+        a = _bricks(bricks)
+        _check(lib().kfx_brick_store_put(self._h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)),
+               "kfx_brick_store_put")
+
+    def __len__(self):
+        n = C.c_int64()
+        _check(lib().kfx_brick_store_count(self._h, C.byref(n)), "kfx_brick_store_count")
+        return int(n.value)
+
+    def take_window(self, origin, dims) -> np.ndarray:
+        """Remove and return the bricks inside the window of voxel `origin` (multiples of 8) and
+        `dims`, ascending (b[2], b[1], b[0])."""
+        o = (C.c_int * 3)(*[int(x) for x in origin])
+        d = (C.c_int * 3)(*[int(x) for x in dims])
+        n = C.c_int64()
+        _check(lib().kfx_brick_store_take_window(self._h, o, d, None, 0, C.byref(n)), "kfx_brick_store_take_window")
+        out = np.zeros(int(n.value), BRICK_DTYPE)
+        if len(out):
+            _check(lib().kfx_brick_store_take_window(self._h, o, d, out.ctypes.data_as(C.c_void_p), len(out),
+                                                     C.byref(n)), "kfx_brick_store_take_window")
+        return out
+
+    def close(self):
+        if self._h:
+            lib().kfx_brick_store_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
     def __del__(self):
         try:
@@ -723,6 +795,40 @@ class KinectFusion:
         a = (C.c_float * 2)()
         _check(lib().kfx_get_shift_ms(self._h, a), "kfx_get_shift_ms")
         return {"evict": a[0], "shift": a[1]}
+
+    def evict_bricks(self, shift, cap: int | None = None) -> np.ndarray:
+        """kfx_evict_bricks: the non-empty bricks `shift` would drop, (N,) BRICK_DTYPE ascending
+        (b[2], b[1], b[0]); the volume is unchanged.  cap None: all of them (a count pass first)."""
+        s = None if shift is None else (C.c_int * 3)(*[int(x) for x in shift])
+        if cap is None:
+            cap = self.evict_brick_count(shift)
+        n = C.c_int64()
+        out = np.zeros(max(cap, 0), BRICK_DTYPE)
+        _check(lib().kfx_evict_bricks(self._h, s, out.ctypes.data_as(C.c_void_p) if cap > 0 else None, max(cap, 0),
+                                      C.byref(n)), "kfx_evict_bricks")
+        return _trim(out, min(n.value, max(cap, 0)))
+
+    def evict_brick_count(self, shift) -> int:
+        """Bricks evict_bricks(shift) would return (count and scan only)."""
+        s = None if shift is None else (C.c_int * 3)(*[int(x) for x in shift])
+        n = C.c_int64()
+        _check(lib().kfx_evict_bricks(self._h, s, None, 0, C.byref(n)), "kfx_evict_bricks")
+        return int(n.value)
+
+    def restore_bricks(self, bricks) -> int:
+        """kfx_restore_bricks: write the (N,) BRICK_DTYPE bricks whose coordinate lies in the
+        current window over the volume; returns how many were written."""
+        a = _bricks(bricks)
+        n = C.c_int64()
+        _check(lib().kfx_restore_bricks(self._h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a),
+                                        C.byref(n)), "kfx_restore_bricks")
+        return int(n.value)
+
+    def stream_ms(self) -> dict:
+        """Device ms of the last evict_bricks and the last restore_bricks (HIP events)."""
+        a = (C.c_float * 2)()
+        _check(lib().kfx_get_stream_ms(self._h, a), "kfx_get_stream_ms")
+        return {"evict_bricks": a[0], "restore_bricks": a[1]}
 
     def extract_mesh(self, cap: int = 50_000_000) -> np.ndarray:
         """Marching-cubes triangles, (N, 3, 3) float32 world coordinates (canonical order)."""

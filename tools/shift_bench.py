@@ -11,7 +11,18 @@ volu_pose comes on top).  Bytes moved = 7 bytes read and 7 written per voxel
 that has a source in the volume, 7 written per cleared voxel (the occupancy
 rebuild reads the 2-byte tsdf once more; it is part of the timed span).
 Prints one JSON record.
-usage: [KFX_LIB_PATH=...] python3 tools/shift_bench.py [out.json [parent commit]]"""
+
+Next to each shift, the bricks out and back in: kfx_evict_bricks
+of the shift (count + scan + emit, kfx_get_stream_ms) and kfx_restore_bricks of
+those bricks over the places they came from (the contents stay what they were;
+the time of the restore does not depend on where the window stands), the same 5
+repetitions after one warm-up, with the brick counts.  Bytes moved: the count
+pass reads 512 B of a brick that shows a weight and all 3584 B of an empty one,
+the emit pass reads 3584 B and writes 3600 B per brick; the restore reads 3600
+B and writes 3584 B per brick and clears the settled bytes.  A second JSON
+record, written to the third argument.
+usage: [KFX_LIB_PATH=...] python3 tools/shift_bench.py [out.json [parent commit [stream_out.json]]]
+       (an empty out.json skips that file)"""
 import hashlib
 import json
 import os
@@ -56,6 +67,28 @@ def main():
             if r:
                 ev.append(kf.shift_ms()["evict"])
         evicted[str(s)], evict_ms[str(s)] = items, stats(ev)
+    stream = {}
+    for s in SHIFTS:  # the bricks of the same slabs, out and back over themselves: the volume stays as it is
+        eb, rb, bricks = [], [], None
+        for r in range(REPS + 1):
+            bricks = kf.evict_bricks(s)
+            if r:
+                eb.append(kf.stream_ms()["evict_bricks"])
+        for r in range(REPS + 1):
+            assert kf.restore_bricks(bricks) == len(bricks)
+            if r and len(bricks):  # (an empty list does no device work and leaves the last figure standing)
+                rb.append(kf.stream_ms()["restore_bricks"])
+        cells = (N // 8) ** 3 - int(np.prod([N // 8 - abs(x) // 8 for x in s]))
+        nb = len(bricks)
+        weighted = int((bricks["weight"].reshape(nb, 512) != 0).any(1).sum())
+        e, h = stats(eb), (stats(rb) if rb else None)
+        out_bytes = 512 * weighted + 3584 * (cells - weighted) + (3584 + 3600) * nb
+        in_bytes = (3600 + 3584) * nb + (N // 8) ** 3
+        stream[str(s)] = {"cells_dropped": cells, "bricks": nb, "record_bytes": 3600 * nb,
+                          "evict_bricks_ms": e, "evict_bytes_moved": out_bytes,
+                          "evict_achieved_TBps": out_bytes / (e["median"] * 1e-3) / 1e12 if e["median"] > 0 else 0.0,
+                          "restore_bricks_ms": h, "restore_bytes_moved": in_bytes,
+                          "restore_achieved_TBps": in_bytes / (h["median"] * 1e-3) / 1e12 if h and h["median"] > 0 else None}
     for s in SHIFTS:
         back = tuple(-x for x in s)
         kept = int(np.prod([N - abs(x) for x in s]))
@@ -99,9 +132,21 @@ def main():
         "host_route_download_upload": sorted(route, key=lambda x: x["total_ms"])[len(route) // 2],
         "host_route_bytes": 2 * 8 * nvox,
     }
+    if len(sys.argv) > 3:
+        sout = {k: out[k] for k in ("workload", "commit_parent", "libkfx_sha256", "copy_rate_TBps")}
+        sout["unit"] = ("ms, device time between HIP events (kfx_get_stream_ms): evict_bricks = count + scan + emit "
+                        "without the copy to the host, restore_bricks = memsets + launch without the upload")
+        sout["set_against"] = "host_route_download_upload of profiles/shift_bench.json (145 ms)"
+        sout["host_route_download_upload"] = out["host_route_download_upload"]
+        sout["shifts"] = stream
+        with open(sys.argv[3], "w") as f:
+            f.write(json.dumps(sout, indent=1) + "\n")
+    out["stream"] = {k: {"bricks": v["bricks"], "evict_bricks_ms": v["evict_bricks_ms"]["median"],
+                         "restore_bricks_ms": v["restore_bricks_ms"] and v["restore_bricks_ms"]["median"]}
+                     for k, v in stream.items()}
     text = json.dumps(out, indent=1)
     print(text)
-    if len(sys.argv) > 1:
+    if len(sys.argv) > 1 and sys.argv[1]:
         os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
         with open(sys.argv[1], "w") as f:
             f.write(text + "\n")
