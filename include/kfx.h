@@ -605,6 +605,67 @@ int kfx_brick_store_count(const kfx_brick_store *s, int64_t *n);
 int kfx_brick_store_take_window(kfx_brick_store *s, const int origin[3], const int dims[3],
                                 kfx_brick *out, int64_t cap, int64_t *n);
 
+/* ---- world map: points and mesh from evicted and window bricks
+ * Added under ABI version 2, nothing else changed.  The extractors above see
+ * the window only; these take the surface from any set of bricks, the window's
+ * merged with what the moving volume streamed out.
+ *
+ * A world is a list of n kfx_brick records, strictly ascending in (b[2], b[1],
+ * b[0]) (the order of kfx_evict_bricks, kfx_brick_store_take_window,
+ * kfx_brick_store_copy and kfx_world_bricks).  World voxel w = 8 b + d holds
+ * the record's values; a voxel of a brick that is not in the list is
+ * unobserved (tsdf 0, weight 0, colour 0).  There are no volume faces: a
+ * neighbour is valid iff its weight != 0.
+ *
+ * kfx_world_points_attr / kfx_world_mesh_attr: the items of
+ * kfx_extract_points_attr / kfx_extract_mesh_attr as defined above, with three
+ * changes.  (1) Every voxel of every listed brick is visited, the +x / +y / +z
+ * edges and cubes of a brick's last row, column and slice included; one that
+ * reaches into an absent brick yields nothing (weight 0).  (2) Position: V_k =
+ * ((float)w_k + 0.5f) * vs_k, vs_k = volu_range[k] / (float)volu_dims[k] of the
+ * context, interpolated along the edge as in the window extractors, then p =
+ * R0 V + t0 with the pose the context was created with (the one
+ * kfx_shift_volume recomputes from), float32 without contraction: a voxel's
+ * position does not depend on where the window stood when it left, and equals
+ * the window extractors' bit for bit while the origin is (0, 0, 0).  (3) Order:
+ * brick (list order), then dz, then lane = 8 dy + dx, then edge axis (points)
+ * or triangle (mesh); for a box of bricks this is the dense canonical order.
+ * Normal and colour as above with R0 as R_volume.
+ * Writes min(cap, total) items, *n = total; cap = 0 counts only; n = 0 gives 0
+ * items and does no device work.  KFX_ERR_ARG, nothing written: a null list
+ * with n > 0, n < 0, a reserved field that is not 0, a list that does not
+ * ascend strictly (duplicates included), a coordinate with |b_k| >= 2^20 (below
+ * that (float)w_k is exact).  KFX_ERR_STATE on a slab of a world larger than 1.
+ * KFX_ERR_OOM when a device buffer cannot be allocated.  The calls run on the
+ * context's stream behind every queued frame and block until the items are on
+ * the host; they read only the list (never the volume), write nothing the
+ * tracker reads, and keep captured graphs and a pending tracking status.  The
+ * device buffers grow on demand, are kept, and are freed in kfx_destroy.
+ *
+ * kfx_get_world_ms: device ms of the last of the two calls: neighbour table,
+ * count + scan, emit (HIP events; neither the upload of the records nor the
+ * download of the items).
+ *
+ * kfx_brick_store_copy: all bricks of the store, ascending, nothing removed;
+ * *n = how many; cap < *n writes nothing.  KFX_ERR_ARG as kfx_brick_store_take_window.
+ *
+ * kfx_world_bricks: the window's non-empty bricks (those kfx_evict_bricks
+ * returns for a shift that drops everything) merged with the store's (NULL: no
+ * store), ascending; the window's brick wins on an equal coordinate.  *n = how
+ * many; cap < *n writes nothing.  Store and volume are unchanged (the last
+ * kfx_evict_bricks time of kfx_get_stream_ms is this call's).
+ *
+ * kfx_save_world_mesh: kfx_world_bricks, kfx_world_mesh_attr (cap_tris <= 0:
+ * KFX_DEFAULT_CLOUD_POINTS triangles), kfx_write_ply_mesh_attr. */
+int kfx_world_points_attr(kfx_ctx *ctx, const kfx_brick *bricks, int64_t n, kfx_vertex *out, int64_t cap,
+                          int64_t *n_points);
+int kfx_world_mesh_attr(kfx_ctx *ctx, const kfx_brick *bricks, int64_t n, kfx_vertex *out, int64_t cap_tris,
+                        int64_t *n_tris);
+int kfx_get_world_ms(kfx_ctx *ctx, float out_ms[3]);
+int kfx_brick_store_copy(const kfx_brick_store *s, kfx_brick *out, int64_t cap, int64_t *n);
+int kfx_world_bricks(kfx_ctx *ctx, const kfx_brick_store *store, kfx_brick *out, int64_t cap, int64_t *n);
+int kfx_save_world_mesh(kfx_ctx *ctx, const kfx_brick_store *store, const char *path, int64_t cap_tris);
+
 /* ---- dataset front-end (host only; no GPU needed) --------------------------
  * depth_sensor in its DATASET build (depth_sensor.cpp:11-46 open, :186-196
  * getFrame) without OpenCV: the PNG files of `<dir>/color` and `<dir>/depth` in

@@ -33,6 +33,10 @@ int set_err(int code, const std::string &msg) {
 
 namespace kfx {
 void set_error_text(const std::string &msg) { g_err = msg; }
+// kfx_brick_store.cpp: the store's bricks (s may be null: none) merged with the
+// nw ascending bricks `win`, ascending, `win` winning an equal coordinate;
+// returns how many there are and writes them when out is not null
+int64_t brick_store_merge(const kfx_brick_store *s, const kfx_brick *win, int64_t nw, kfx_brick *out);
 }  // namespace kfx
 
 namespace {
@@ -248,7 +252,15 @@ struct kfx_ctx {
   // kfx_evict_bricks [0, 1] and the last kfx_restore_bricks [2, 3]
   hipEvent_t ev_stream[4]{};
   bool stream_timed[2] = {false, false};
-  uint8_t *mc_tab = nullptr;      // marching-cubes table (uploaded on first use)
+  // world map: the uploaded records, the neighbour table's
+  // keys and entries, the count / scan workspace and the items (each grown on
+  // demand, kept, freed in kfx_destroy), and the events around the last call's
+  // table [0, 1], count + scan [1, 2] and emit [3, 4]
+  void *world_buf[5]{};
+  size_t world_cap[5]{};
+  hipEvent_t ev_world[5]{};
+  float world_ms[3]{};
+  uint8_t *mc_tab = nullptr;     // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded
   // march left unexamined, and the hit payload
@@ -1335,6 +1347,10 @@ int kfx_destroy(kfx_ctx *c) {
   for (hipEvent_t e : c->ev_shift)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_stream)
+    if (e) (void)hipEventDestroy(e);
+  for (void *b : c->world_buf)
+    if (b) (void)hipFree(b);
+  for (hipEvent_t e : c->ev_world)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -3457,6 +3473,170 @@ int kfx_get_stream_ms(kfx_ctx *c, float out_ms[2]) {
     HIPCHK(hipEventElapsedTime(&out_ms[k], c->ev_stream[2 * k], c->ev_stream[2 * k + 1]));
   }
   return KFX_OK;
+}
+
+// ---- world map -------------------------------------------------
+
+// the list checks kfx_world_points_attr and kfx_world_mesh_attr share
+static int world_args(kfx_ctx *c, const kfx_brick *bricks, int64_t n, const void *out, int64_t cap) {
+  if (n < 0 || (n > 0 && !bricks)) return set_err(KFX_ERR_ARG, "bad brick list");
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad item buffer");
+  if (c->slab && c->world > 1)
+    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
+  for (int64_t i = 0; i < n; ++i) {
+    const kfx_brick &b = bricks[i];
+    if (b.reserved != 0) return set_err(KFX_ERR_ARG, "world: a reserved field that is not 0");
+    for (int k = 0; k < 3; ++k)
+      if (b.b[k] <= -(1 << 20) || b.b[k] >= (1 << 20))
+        return set_err(KFX_ERR_ARG, "world: a brick coordinate outside (-2^20, 2^20)");
+    if (i > 0) {
+      const kfx_brick &a = bricks[i - 1];
+      const bool up = a.b[2] != b.b[2] ? a.b[2] < b.b[2] : (a.b[1] != b.b[1] ? a.b[1] < b.b[1] : a.b[0] < b.b[0]);
+      if (!up) return set_err(KFX_ERR_ARG, "world: the bricks must ascend strictly in (b[2], b[1], b[0])");
+    }
+  }
+  return KFX_OK;
+}
+
+// grow one of the world buffers to at least `bytes` (kept; the previous call
+// has completed: every world call ends with a sync)
+static int world_reserve(kfx_ctx *c, int which, size_t bytes) {
+  if (c->world_cap[which] >= bytes) return KFX_OK;
+  if (c->world_buf[which]) (void)hipFree(c->world_buf[which]);
+  c->world_buf[which] = nullptr;
+  c->world_cap[which] = 0;
+  if (hipMalloc(&c->world_buf[which], bytes) != hipSuccess) {
+    c->world_buf[which] = nullptr;
+    (void)hipGetLastError();
+    return set_err(KFX_ERR_OOM, "world: hipMalloc(" + std::to_string(bytes) + ")");
+  }
+  c->world_cap[which] = bytes;
+  return KFX_OK;
+}
+
+// kfx_world_points_attr / kfx_world_mesh_attr: `out` holds cap items of 1 / 3 kfx_vertex
+static int world_items(kfx_ctx *c, const kfx_brick *bricks, int64_t n, bool mesh, kfx_vertex *out, int64_t cap,
+                       int64_t *n_items) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = world_args(c, bricks, n, out, cap))) return r;
+  for (float &m : c->world_ms) m = 0.f;
+  if (n == 0) {  // no device work
+    if (n_items) *n_items = 0;
+    return KFX_OK;
+  }
+  if (n > ((int64_t)1 << 28)) return set_err(KFX_ERR_OOM, "world: more bricks than the record buffer can hold");
+  for (hipEvent_t &e : c->ev_world)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  if (mesh && !c->mc_tab) {
+    uint8_t tab[256 * 16];
+    build_mc_table(tab);
+    if ((r = dalloc(c, (void **)&c->mc_tab, sizeof(tab)))) return r;
+    HIPCHK(hipMemcpy(c->mc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+  }
+  const size_t nn = (size_t)n, nb = scan_blocks(nn);
+  const size_t o_off = (nn * 4 + 7) & ~(size_t)7;
+  if ((r = world_reserve(c, 0, nn * sizeof(kfx_brick))) || (r = world_reserve(c, 1, nn * 8)) ||
+      (r = world_reserve(c, 2, nn * 27 * 4)) || (r = world_reserve(c, 3, o_off + nn * 8 + nb * 8 + 64)))
+    return r;
+  unsigned long long *keys = (unsigned long long *)c->world_buf[1];
+  int32_t *neigh = (int32_t *)c->world_buf[2];
+  char *ws = (char *)c->world_buf[3];
+  unsigned *counts = (unsigned *)ws;
+  unsigned long long *offsets = (unsigned long long *)(ws + o_off);
+  unsigned long long *bsum = offsets + nn;
+  unsigned long long *dtot = bsum + nb;
+  const uint8_t *tab = mesh ? c->mc_tab : nullptr;
+  const DevPose p0 = to_dev(c->volu_pose0);  // (R0, t0): a voxel's position does not depend on where the window stands
+  hipStream_t s = c->stream;                 // behind every queued frame
+  HIPCHK(hipMemcpyAsync(c->world_buf[0], bricks, nn * sizeof(kfx_brick), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(c->ev_world[0], s));
+  launch_world_neigh(s, c->world_buf[0], nn, keys, neigh);
+  HIPCHK(hipEventRecord(c->ev_world[1], s));
+  launch_world_sweep(s, c->world_buf[0], nn, neigh, p0, c->vol.vs, tab, counts, nullptr, nullptr, 0);
+  launch_scan(s, counts, offsets, bsum, nn, dtot);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_world[2], s));
+  unsigned long long ht = 0;
+  HIPCHK(hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const int64_t total = (int64_t)ht, m = std::min<int64_t>(total, cap);
+  if (m > 0) {
+    const size_t bytes = (size_t)m * (mesh ? 3 : 1) * sizeof(kfx_vertex);
+    if ((r = world_reserve(c, 4, bytes))) return r;
+    HIPCHK(hipEventRecord(c->ev_world[3], s));
+    launch_world_sweep(s, c->world_buf[0], nn, neigh, p0, c->vol.vs, tab, counts, offsets, (float *)c->world_buf[4],
+                       (unsigned long long)m);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_world[4], s));
+    HIPCHK(hipMemcpyAsync(out, c->world_buf[4], bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipEventElapsedTime(&c->world_ms[2], c->ev_world[3], c->ev_world[4]));
+  }
+  HIPCHK(hipEventElapsedTime(&c->world_ms[0], c->ev_world[0], c->ev_world[1]));
+  HIPCHK(hipEventElapsedTime(&c->world_ms[1], c->ev_world[1], c->ev_world[2]));
+  if (n_items) *n_items = total;
+  return KFX_OK;
+}
+
+int kfx_world_points_attr(kfx_ctx *c, const kfx_brick *bricks, int64_t n, kfx_vertex *out, int64_t cap,
+                          int64_t *n_points) {
+  return world_items(c, bricks, n, false, out, cap, n_points);
+}
+int kfx_world_mesh_attr(kfx_ctx *c, const kfx_brick *bricks, int64_t n, kfx_vertex *out, int64_t cap_tris,
+                        int64_t *n_tris) {
+  return world_items(c, bricks, n, true, out, cap_tris, n_tris);
+}
+
+int kfx_get_world_ms(kfx_ctx *c, float out_ms[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  for (int k = 0; k < 3; ++k) out_ms[k] = c->world_ms[k];
+  return KFX_OK;
+}
+
+int kfx_world_bricks(kfx_ctx *c, const kfx_brick_store *store, kfx_brick *out, int64_t cap, int64_t *n) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!n) return set_err(KFX_ERR_ARG, "null count");
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad brick buffer");
+  // the window's non-empty bricks: what a shift that drops everything evicts
+  const int all[3] = {(c->vol.X + 7) / 8 * 8, 0, 0};
+  int64_t nw = 0;
+  if ((r = kfx_evict_bricks(c, all, nullptr, 0, &nw))) return r;
+  std::vector<kfx_brick> win;
+  try {
+    win.resize((size_t)nw);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "world_bricks: out of memory");
+  }
+  if (nw > 0 && (r = kfx_evict_bricks(c, all, win.data(), nw, &nw))) return r;
+  *n = brick_store_merge(store, win.data(), nw, nullptr);
+  if (cap < *n) return KFX_OK;  // nothing written: size the buffer and call again
+  (void)brick_store_merge(store, win.data(), nw, out);
+  return KFX_OK;
+}
+
+int kfx_save_world_mesh(kfx_ctx *c, const kfx_brick_store *store, const char *path, int64_t cap) {
+  if (!path) return set_err(KFX_ERR_ARG, "null path");
+  if (cap <= 0) cap = KFX_DEFAULT_CLOUD_POINTS;
+  int64_t nb = 0, total = 0;
+  int r = kfx_world_bricks(c, store, nullptr, 0, &nb);
+  if (r) return r;
+  std::vector<kfx_brick> bricks;
+  std::vector<kfx_vertex> v;
+  try {
+    bricks.resize((size_t)nb);
+    if (nb > 0 && (r = kfx_world_bricks(c, store, bricks.data(), nb, &nb))) return r;
+    if ((r = kfx_world_mesh_attr(c, bricks.data(), nb, nullptr, 0, &total))) return r;
+    v.resize((size_t)std::min(total, cap) * 3);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "save_world_mesh: out of memory");
+  }
+  const int64_t m = std::min(total, cap);
+  if (m > 0 && (r = kfx_world_mesh_attr(c, bricks.data(), nb, v.data(), m, &total))) return r;
+  return kfx_write_ply_mesh_attr(path, v.data(), m);
 }
 
 int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *vp, const kfx_pose *cam, float ahead_m, int shift[3]) {

@@ -36,6 +36,32 @@ struct kfx_brick_store {
   std::map<Key, std::unique_ptr<kfx_brick>> bricks;
 };
 
+namespace kfx {
+
+// the store's bricks (s may be null: none) merged with the nw ascending bricks
+// `win` (kfx_world_bricks: the window's), ascending, `win` winning an equal
+// coordinate; returns how many there are and writes them when out is not null
+int64_t brick_store_merge(const kfx_brick_store *s, const kfx_brick *win, int64_t nw, kfx_brick *out) {
+  static const std::map<Key, std::unique_ptr<kfx_brick>> none;
+  const auto &held = s ? s->bricks : none;
+  auto it = held.begin();
+  int64_t i = 0, at = 0;
+  while (it != held.end() || i < nw) {
+    const kfx_brick *src;
+    if (it == held.end() || (i < nw && !(it->first < key_of(win[i])))) {
+      if (it != held.end() && it->first == key_of(win[i])) ++it;  // the window's brick wins
+      src = &win[i++];
+    } else {
+      src = (it++)->second.get();
+    }
+    if (out) std::memcpy(&out[at], src, sizeof(kfx_brick));
+    ++at;
+  }
+  return at;
+}
+
+}  // namespace kfx
+
 extern "C" {
 
 int kfx_brick_store_create(kfx_brick_store **out) {
@@ -70,6 +96,16 @@ int kfx_brick_store_put(kfx_brick_store *s, const kfx_brick *in, int64_t n) {
 int kfx_brick_store_count(const kfx_brick_store *s, int64_t *n) {
   if (!s || !n) return fail(KFX_ERR_ARG, "null argument");
   *n = (int64_t)s->bricks.size();
+  return KFX_OK;
+}
+
+int kfx_brick_store_copy(const kfx_brick_store *s, kfx_brick *out, int64_t cap, int64_t *n) {
+  if (!s || !n) return fail(KFX_ERR_ARG, "null argument");
+  if (cap < 0 || (cap > 0 && !out)) return fail(KFX_ERR_ARG, "bad brick buffer");
+  *n = (int64_t)s->bricks.size();
+  if (cap < *n) return KFX_OK;  // nothing written: size the buffer and call again
+  int64_t at = 0;
+  for (const auto &e : s->bricks) std::memcpy(&out[at++], e.second.get(), sizeof(kfx_brick));
   return KFX_OK;
 }
 

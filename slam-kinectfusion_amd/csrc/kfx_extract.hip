@@ -45,135 +45,9 @@ __device__ __forceinline__ bool brick_clear(const VolView &v, int tile, int c0) 
   return !((v.bocc[(size_t)tile * v.bw + (lbz >> 6)] >> (lbz & 63)) & 1ull);
 }
 
-// One extraction wave's brick (lanes = the tile's 64 columns, slices [z0, z1)):
-// kEmit = false returns the wave's point count; true writes the points at
-// base + (canonical rank) (rank < cap only) and returns the count too.
-// kAttr (emit only): 7-word attributed points (kfx_vertex) instead of float3.
-template <bool kEmit, bool kAttr = false>
-__device__ __forceinline__ unsigned extract_wave(const VolView &v, const DevPose &aff, int x, int y, int z0,
-                                                 int z1, unsigned long long base, float *out,
-                                                 unsigned long long cap) {
-  const int lane = threadIdx.x & 63;
-  unsigned total = 0;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int z = z0; z < z1; ++z) {
-    f3 pts[3];
-    int axes = 0;
-    const int n = extract_voxel<kEmit && kAttr>(v, aff, x, y, z, pts, &axes);
-    const unsigned long long b1 = __ballot(n >= 1), b2 = __ballot(n >= 2), b3 = __ballot(n >= 3);
-    if (kEmit) {
-      const unsigned long long r = base + (unsigned long long)(__popcll(b1 & below) +
-                                                               __popcll(b2 & below) +
-                                                               __popcll(b3 & below));
-#pragma unroll
-      for (int l = 0; l < 3; ++l)  // (unrolled: pts stays in registers)
-        if (l < n && r + l < cap) {
-          if constexpr (kAttr) {
-            uint32_t *dst = reinterpret_cast<uint32_t *>(out) + (size_t)(r + l) * kVertexWords;
-            st_vertex(dst, pts[l]);
-            vertex_attr(v, aff, x, y, z, (axes >> (2 * l)) & 3, dst + 3);
-          } else {
-            st3(out, (size_t)(r + l), pts[l]);
-          }
-        }
-    }
-    const unsigned wt = (unsigned)(__popcll(b1) + __popcll(b2) + __popcll(b3));
-    base += wt;
-    total += wt;
-  }
-  return total;
-}
-
-// Marching cubes (§8 f5; C5 asks for a mesh, the reference has none).  Cube
-// (x, y, z) = the 8 voxels (x+dx, y+dy, z+dz); all 8 must have weight > 0;
-// corner c = dx | dy<<1 | dz<<2 is inside when its tsdf < 0.  `tab` (256 x
-// 16 bytes, built by the host, kfx_api.hip mc_table) lists per configuration
-// the triangles as edge indices (edge e: axis e/4, the 4 edges of an axis in
-// ascending lower-corner order).  An edge vertex interpolates the two voxel
-// centres as the point extraction does (FullScan6, tsdf_volume.cu:341-360),
-// then the volume pose.  Triangles come out in the canonical order of the
-// point cloud (8-slice chunk, tile, z, lane, triangle), 9 floats each.
-// kAttr: also writes the 7-word attributed vertex (kfx_vertex) to dst.
-template <bool kAttr = false>
-__device__ __forceinline__ f3 mc_vertex(const VolView &v, const DevPose &aff, int x, int y, int z, int e,
-                                        const float (&F)[8], uint32_t *dst = nullptr) {
-  const int a = e >> 2, k = e & 3;
-  // lower corner of edge e: the k-th corner (ascending) with bit a clear
-  int c = 0, m = 0;
-  for (int q = 0; q < 8; ++q)
-    if (!((q >> a) & 1)) {
-      if (m == k) c = q;
-      ++m;
-    }
-  const int cn = c | (1 << a);
-  f3 V = {((float)(x + (c & 1)) + 0.5f) * v.vs[0], ((float)(y + ((c >> 1) & 1)) + 0.5f) * v.vs[1],
-          ((float)(z + ((c >> 2) & 1)) + 0.5f) * v.vs[2]};
-  const float Fa = F[c], Fb = F[cn];
-  const float Va = a == 0 ? V.x : (a == 1 ? V.y : V.z);
-  const float Vn = Va + v.vs[a];
-  const float d_inv = 1.f / (fabsf(Fa) + fabsf(Fb));
-  const float cc = (Va * fabsf(Fb) + Vn * fabsf(Fa)) * d_inv;
-  if (a == 0) V.x = cc;
-  else if (a == 1) V.y = cc;
-  else V.z = cc;
-  const f3 p = add(rmul(aff.R, V), {aff.t[0], aff.t[1], aff.t[2]});
-  if constexpr (kAttr) {
-    st_vertex(dst, p);
-    vertex_attr(v, aff, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1), a, dst + 3);
-  }
-  return p;
-}
-
-// One marching-cubes wave's brick (as extract_wave): triangles in the
-// canonical order, 9 floats each.
-// kAttr (emit only): 21 words per triangle (3 kfx_vertex).
-template <bool kEmit, bool kAttr = false>
-__device__ __forceinline__ unsigned mesh_wave(const VolView &v, const DevPose &aff, const uint8_t *__restrict__ tab,
-                                              int x, int y, int z0, int z1, unsigned long long base, float *out,
-                                              unsigned long long cap) {
-  const int lane = threadIdx.x & 63;
-  unsigned total = 0;
-  for (int z = z0; z < z1; ++z) {
-    float F[8];
-    int cfg = 0, nt = 0;
-    if (x + 1 < v.X && y + 1 < v.Y) {
-      bool all = true;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const size_t i = vox_index(v, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1));
-        all = all && v.weight[i] > 0;
-        F[c] = (float)v.tsdf[i] * kDivShortMax;
-        cfg |= (F[c] < 0.f ? 1 : 0) << c;
-      }
-      if (all) nt = tab[16 * cfg];
-    }
-    // wave prefix of the triangle counts (lane order)
-    int incl = nt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off);
-      if (lane >= off) incl += o;
-    }
-    if (kEmit) {
-      const unsigned long long r0 = base + (unsigned long long)(incl - nt);
-      for (int t = 0; t < nt; ++t) {
-        if (r0 + t >= cap) break;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          if constexpr (kAttr)
-            (void)mc_vertex<true>(v, aff, x, y, z, tab[16 * cfg + 1 + 3 * t + k], F,
-                                  reinterpret_cast<uint32_t *>(out) + (size_t)(3 * (r0 + t) + k) * kVertexWords);
-          else
-            st3(out, (size_t)(3 * (r0 + t) + k), mc_vertex(v, aff, x, y, z, tab[16 * cfg + 1 + 3 * t + k], F));
-        }
-      }
-    }
-    const unsigned wt = (unsigned)__shfl(incl, 63);
-    base += wt;
-    total += wt;
-  }
-  return total;
-}
+// The brick sweeps of one wave (extract_wave, mesh_wave, mc_vertex) live in
+// kfx_extract_dev.h too: the world extraction (kfx_world.hip) runs them on a
+// staged brick.
 
 // Extraction with ONE read of the volume (points or marching cubes).
 // Pass A (k_extract_pool): each canonical wave counts its brick's items and,

@@ -1,5 +1,5 @@
 // kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip,
-// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip) and the host runtime (kfx_api.hip).  Not part of the public ABI.
+// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip) and the host runtime (kfx_api.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -431,6 +431,21 @@ void launch_brick_emit(hipStream_t s, const VolView &v, const int shift[3], cons
 // bricks (no two for one brick); the occupancy maps gain their marks, every
 // settled byte is cleared and the gate opened
 void launch_brick_restore(hipStream_t s, const VolView &v, const int origin[3], const void *in, size_t n);
+
+// ---- kfx_world.hip --------------------------------------------------------
+// the world map.  recs: n kfx_brick records in device memory,
+// strictly ascending (b[2], b[1], b[0]), every |b_k| < 2^20 (the host checks).
+// keys[n] (workspace), neigh[n][27] = the list index of each brick's 27
+// neighbours (slot ((oz + 1) * 3 + oy + 1) * 3 + ox + 1), -1 where absent
+void launch_world_neigh(hipStream_t s, const void *recs, size_t n, unsigned long long *keys, int32_t *neigh);
+// one block per brick, on the brick and its halo staged in LDS: offsets == null
+// counts[brick] = its attributed points (tab == null) or marching-cubes
+// triangles (tab: launch_mesh's table), else the items (7 words per vertex) at
+// offsets[brick] (< cap).  Positions from pose0 (the creation pose) and the
+// world voxel index 8 b + d, voxel size vs.
+void launch_world_sweep(hipStream_t s, const void *recs, size_t n, const int32_t *neigh, DevPose pose0,
+                        const float vs[3], const uint8_t *tab, unsigned *counts, const unsigned long long *offsets,
+                        float *out, unsigned long long cap);
 
 // ---- kfx_volume_io.hip ----------------------------------------------------
 void launch_export_records(hipStream_t s, VolView v, int z0, int nz, uint64_t *dst);

@@ -11,9 +11,12 @@
 // brick store, kfx_evict_bricks / kfx_brick_store_put, and those of the new
 // window come back, kfx_brick_store_take_window / kfx_restore_bricks.  The
 // followed cloud keeps its meaning, the points evicted at each shift, then the
-// final window: a surface that left and returned appears once per departure).
+// final window: a surface that left and returned appears once per departure;
+// a ninth argument, with the eighth, writes the world mesh at the end, DESIGN.md
+// §22: the window's bricks merged with the store's, kfx_save_world_mesh, every
+// surface once wherever the window stands).
 //   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
-//                  [followed_cloud.ply] [stream]
+//                  [followed_cloud.ply] [stream] [world_mesh.ply]
 #include <chrono>
 #include <cstdio>
 #include <vector>
@@ -24,7 +27,7 @@ int main(int argc, char **argv) {
   if (argc < 2) {
     std::fprintf(stderr,
                  "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm] "
-                 "[followed_cloud.ply] [stream]\n",
+                 "[followed_cloud.ply] [stream] [world_mesh.ply]\n",
                  argv[0]);
     return 2;
   }
@@ -180,6 +183,21 @@ int main(int argc, char **argv) {
     }
     std::printf("followed: %d shifts, %lld evicted points, %lld in the volume\n", shifts, (long long)at,
                 (long long)nf);
+  }
+  if (stream && argc > 9 && argv[9][0]) {  // the world map: what the window holds and what it left behind
+    int64_t nb = 0, nt = 0;
+    if (kfx_world_bricks(ctx, store, nullptr, 0, &nb) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    bricks.resize((size_t)nb);
+    if ((nb > 0 && kfx_world_bricks(ctx, store, bricks.data(), nb, &nb) != KFX_OK) ||
+        kfx_world_mesh_attr(ctx, bricks.data(), nb, nullptr, 0, &nt) != KFX_OK ||
+        kfx_save_world_mesh(ctx, store, argv[9], 0) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    std::printf("world: %lld bricks, %lld triangles\n", (long long)nb, (long long)nt);
   }
   if (stream) {
     int64_t held = 0;

@@ -44,6 +44,8 @@ EXPORTS = [
     "kfx_shift_for_pose",
     "kfx_evict_bricks", "kfx_restore_bricks", "kfx_get_stream_ms", "kfx_brick_store_create", "kfx_brick_store_destroy",
     "kfx_brick_store_put", "kfx_brick_store_count", "kfx_brick_store_take_window",
+    "kfx_world_points_attr", "kfx_world_mesh_attr", "kfx_get_world_ms", "kfx_brick_store_copy", "kfx_world_bricks",
+    "kfx_save_world_mesh",
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks", "kfx_debug_extract_units", "kfx_debug_scan",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
@@ -163,6 +165,12 @@ def lib():
         "kfx_brick_store_put": ([vp, vp, C.c_int64], i),
         "kfx_brick_store_count": ([vp, P(C.c_int64)], i),
         "kfx_brick_store_take_window": ([vp, P(i), P(i), vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_world_points_attr": ([vp, vp, C.c_int64, vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_world_mesh_attr": ([vp, vp, C.c_int64, vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_get_world_ms": ([vp, P(f)], i),
+        "kfx_brick_store_copy": ([vp, vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_world_bricks": ([vp, vp, vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_save_world_mesh": ([vp, vp, C.c_char_p, C.c_int64], i),
         "kfx_volume_checksum": ([vp, P(C.c_uint64)], i),
         "kfx_write_ply": ([C.c_char_p, P(f), C.c_int64], i),
         "kfx_save_pointcloud": ([vp, C.c_char_p, C.c_int64], i),
@@ -381,6 +389,16 @@ class BrickStore:
         if len(out):
             _check(lib().kfx_brick_store_take_window(self._h, o, d, out.ctypes.data_as(C.c_void_p), len(out),
                                                      C.byref(n)), "kfx_brick_store_take_window")
+        return out
+
+    def copy(self) -> np.ndarray:
+        """All bricks of the store, ascending (b[2], b[1], b[0]); nothing is removed."""
+        n = C.c_int64()
+        _check(lib().kfx_brick_store_copy(self._h, None, 0, C.byref(n)), "kfx_brick_store_copy")
+        out = np.zeros(int(n.value), BRICK_DTYPE)
+        if len(out):
+            _check(lib().kfx_brick_store_copy(self._h, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)),
+                   "kfx_brick_store_copy")
         return out
 
     def close(self):
@@ -829,6 +847,59 @@ class KinectFusion:
         a = (C.c_float * 2)()
         _check(lib().kfx_get_stream_ms(self._h, a), "kfx_get_stream_ms")
         return {"evict_bricks": a[0], "restore_bricks": a[1]}
+
+    # ---- world map ------------------------------------------
+    def _world(self, bricks, cap: int, mesh: bool) -> np.ndarray:
+        a = _bricks(bricks)
+        name = "kfx_world_mesh_attr" if mesh else "kfx_world_points_attr"
+        n = C.c_int64()
+        cap = max(int(cap), 0)
+        out = np.empty((cap, 3) if mesh else cap, np.dtype(VERTEX_DTYPE))
+        _check(getattr(lib(), name)(self._h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a),
+                                    out.ctypes.data_as(C.c_void_p) if cap > 0 else None, cap, C.byref(n)), name)
+        return _trim(out, min(n.value, cap))
+
+    def world_points(self, bricks, cap: int = 10_000_000) -> np.ndarray:
+        """kfx_world_points_attr: the attributed points of the (N,) BRICK_DTYPE world `bricks`
+        (strictly ascending (b[2], b[1], b[0])), (M,) VERTEX_DTYPE."""
+        return self._world(bricks, cap, False)
+
+    def world_mesh(self, bricks, cap: int = 50_000_000) -> np.ndarray:
+        """kfx_world_mesh_attr: the attributed triangles of the world `bricks`, (M, 3) VERTEX_DTYPE."""
+        return self._world(bricks, cap, True)
+
+    def world_count(self, bricks, mesh: bool = False) -> int:
+        """Points (or triangles) the world `bricks` holds (table, count and scan only)."""
+        a = _bricks(bricks)
+        name = "kfx_world_mesh_attr" if mesh else "kfx_world_points_attr"
+        n = C.c_int64()
+        _check(getattr(lib(), name)(self._h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a), None, 0,
+                                    C.byref(n)), name)
+        return int(n.value)
+
+    def world_bricks(self, store: "BrickStore | None" = None) -> np.ndarray:
+        """kfx_world_bricks: the window's non-empty bricks merged with the store's (the window's
+        win), (N,) BRICK_DTYPE ascending; store and volume are unchanged."""
+        h = store._h if store is not None else None
+        n = C.c_int64()
+        _check(lib().kfx_world_bricks(self._h, h, None, 0, C.byref(n)), "kfx_world_bricks")
+        out = np.zeros(int(n.value), BRICK_DTYPE)
+        if len(out):
+            _check(lib().kfx_world_bricks(self._h, h, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)),
+                   "kfx_world_bricks")
+        return out
+
+    def save_world_mesh(self, path: str, store: "BrickStore | None" = None, cap: int = 0):
+        """kfx_save_world_mesh: the world's attributed mesh (window and store) as an ASCII PLY."""
+        _check(lib().kfx_save_world_mesh(self._h, store._h if store is not None else None, path.encode(), cap),
+               "kfx_save_world_mesh")
+
+    def world_ms(self) -> dict:
+        """Device ms of the last world_points / world_mesh / world_count: the neighbour table,
+        count + scan, emit (HIP events; without the upload of the records)."""
+        a = (C.c_float * 3)()
+        _check(lib().kfx_get_world_ms(self._h, a), "kfx_get_world_ms")
+        return {"table": a[0], "count": a[1], "emit": a[2]}
 
     def extract_mesh(self, cap: int = 50_000_000) -> np.ndarray:
         """Marching-cubes triangles, (N, 3, 3) float32 world coordinates (canonical order)."""

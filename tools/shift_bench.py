@@ -21,7 +21,18 @@ pass reads 512 B of a brick that shows a weight and all 3584 B of an empty one,
 the emit pass reads 3584 B and writes 3600 B per brick; the restore reads 3600
 B and writes 3584 B per brick and clears the settled bytes.  A second JSON
 record, written to the third argument.
-usage: [KFX_LIB_PATH=...] python3 tools/shift_bench.py [out.json [parent commit [stream_out.json]]]
+
+The world map, a third JSON record, written to the fourth
+argument: after the 30 frames and before any shift, kfx_world_points_attr and
+kfx_world_mesh_attr of kfx_world_bricks() (the window's non-empty bricks, no
+store), device ms of the neighbour table, count + scan and emit from
+kfx_get_world_ms, and next to them kfx_extract_points_attr /
+kfx_extract_mesh_attr of the same window in the same process (kfx_get_extract_ms)
+as the yardstick; median of 5 after one warm-up, with the brick count, the
+items and the bytes read.  The upload of the records over PCIe (3600 B per
+brick and call) is not in the device figures; the call's wall time is given
+next to them.  With the first and third argument empty only this part runs.
+usage: [KFX_LIB_PATH=...] python3 tools/shift_bench.py [out.json [parent commit [stream_out.json [world_out.json]]]]
        (an empty out.json skips that file)"""
 import hashlib
 import json
@@ -49,6 +60,45 @@ def stats(xs):
     return {"min": xs[0], "median": xs[len(xs) // 2], "max": xs[-1], "all": xs}
 
 
+def world_bench(kf):
+    """The world map against the dense extractors on the volume as it stands."""
+    bricks = kf.world_bricks()
+    n = len(bricks)
+    negative = int((bricks["tsdf"].reshape(n, -1) < 0).any(1).sum())
+    out = {"bricks": n, "bricks_with_a_negative_tsdf": negative, "record_bytes": 3600 * n}
+    for mesh in (False, True):
+        parts, wall, dense, items, ditems = {"table": [], "count": [], "emit": []}, [], {"count": [], "scan": [], "emit": []}, 0, 0
+        passes = 0
+        for r in range(REPS + 1):  # the first repetition warms up (buffers, events, kernels)
+            t0 = time.perf_counter()
+            items = len(kf.world_mesh(bricks) if mesh else kf.world_points(bricks))
+            t1 = time.perf_counter()
+            ms = kf.world_ms()
+            ditems = len(kf.extract_mesh_attr() if mesh else kf.extract_points_attr())
+            dms = kf.extract_ms()
+            passes = dms["passes"]
+            if r:
+                wall.append((t1 - t0) * 1e3)
+                for k in parts:
+                    parts[k].append(ms[k])
+                for k in dense:
+                    dense[k].append(dms[k])
+        w = {k: stats(v) for k, v in parts.items()}
+        d = {k: stats(v) for k, v in dense.items()}
+        out["mesh" if mesh else "points"] = {
+            "items": items, "item_bytes_written": items * (84 if mesh else 28),
+            "world_ms": w, "world_ms_total_median": sum(w[k]["median"] for k in w),
+            "world_call_wall_ms": stats(wall),
+            # the count pass gathers every brick's tile: 363 x-rows of 16 B of tsdf + 8 B of weight (each record is
+            # read by up to 27 tiles; the repeats hit the caches); the emit pass gathers the bricks with items
+            # only, 32 B of colour per row too
+            "count_gather_bytes_requested": 363 * 24 * n, "emit_gather_bytes_per_brick_with_items": 363 * 56,
+            "window_items": ditems, "window_extract_ms": d, "window_extract_passes": passes,
+            "window_extract_ms_total_median": sum(d[k]["median"] for k in d),
+        }
+    return out
+
+
 def main():
     intr = synth.Intrinsics.vga()
     p = default_params(dims=N, range_m=2.048)
@@ -58,6 +108,29 @@ def main():
     for i in synth.ping_pong(48, WARM_FRAMES):
         kf.pipeline_staged(int(i))
     kf.synchronize()
+    commit = sys.argv[2] if len(sys.argv) > 2 else ""  # (a copy of the tree without its history: give it)
+    if not commit:
+        try:
+            commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True,
+                                    text=True).stdout.strip()
+        except OSError:
+            pass
+    workload = "C2 640x480, 512^3 @ 4 mm, %d frames of the bench sequence (ping-pong over 48)" % WARM_FRAMES
+    sha = hashlib.sha256(open(kfx.LIB_PATH, "rb").read()).hexdigest()
+    if len(sys.argv) > 4 and sys.argv[4]:
+        wout = {"workload": workload, "commit_parent": commit, "libkfx_sha256": sha,
+                "unit": ("ms, device time between HIP events: world = neighbour table, count + scan, emit "
+                         "(kfx_get_world_ms; neither the upload of the records nor the download of the items), window = "
+                         "kfx_get_extract_ms of kfx_extract_*_attr; wall = the whole world call, upload and download included"),
+                "world": world_bench(kf)}
+        with open(sys.argv[4], "w") as f:
+            f.write(json.dumps(wout, indent=1) + "\n")
+        print(json.dumps({k: {"items": v["items"], "world_ms": v["world_ms_total_median"],
+                              "window_ms": v["window_extract_ms_total_median"]}
+                          for k, v in wout["world"].items() if isinstance(v, dict)}))
+        if not (len(sys.argv) > 1 and sys.argv[1]) and not sys.argv[3]:
+            kf.close()
+            return
     nvox = N ** 3
     rec, evicted, evict_ms = {}, {}, {}
     for s in SHIFTS:  # every eviction before the first shift: it changes nothing, and the slabs still hold their surfaces
@@ -115,18 +188,11 @@ def main():
         t2 = time.perf_counter()
         route.append({"download_ms": (t1 - t0) * 1e3, "upload_ms": (t2 - t1) * 1e3, "total_ms": (t2 - t0) * 1e3})
     kf.close()
-    commit = sys.argv[2] if len(sys.argv) > 2 else ""  # (a copy of the tree without its history: give it)
-    if not commit:
-        try:
-            commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True,
-                                    text=True).stdout.strip()
-        except OSError:
-            pass
     out = {
-        "workload": "C2 640x480, 512^3 @ 4 mm, %d frames of the bench sequence (ping-pong over 48)" % WARM_FRAMES,
+        "workload": workload,
         "unit": "ms, device time between HIP events around the launches (kfx_get_shift_ms); the host route: wall ms",
         "commit_parent": commit,
-        "libkfx_sha256": hashlib.sha256(open(kfx.LIB_PATH, "rb").read()).hexdigest(),
+        "libkfx_sha256": sha,
         "copy_rate_TBps": COPY_TBS,
         "shifts": rec,
         "host_route_download_upload": sorted(route, key=lambda x: x["total_ms"])[len(route) // 2],
