@@ -12,41 +12,23 @@
 #include <string>
 #include <vector>
 
-#include <rccl/rccl.h>
-
-#include "../../include/kfx.h"
-#include "kfx_internal.h"
+#include "kfx_ctx.h"
+#include "kfx_scanws.h"
 #include "kfx_settled.h"
-
-using namespace kfx;
 
 namespace {
 
 thread_local std::string g_err;
 
+}  // namespace
+
+namespace kfx {
+
 int set_err(int code, const std::string &msg) {
   g_err = msg;
   return code;
 }
-
-}  // namespace
-
-namespace kfx {
 void set_error_text(const std::string &msg) { g_err = msg; }
-// kfx_brick_store.cpp: the store's bricks (s may be null: none) merged with the
-// nw ascending bricks `win`, ascending, `win` winning an equal coordinate;
-// returns how many there are and writes them when out is not null
-int64_t brick_store_merge(const kfx_brick_store *s, const kfx_brick *win, int64_t nw, kfx_brick *out);
-}  // namespace kfx
-
-namespace {
-
-#define HIPCHK(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return set_err(KFX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
 DevPose to_dev(const kfx_pose &p) {
   DevPose d;
@@ -60,6 +42,11 @@ kfx_pose to_api(const DevPose &d) {
   std::memcpy(p.t, d.t, sizeof(p.t));
   return p;
 }
+
+}  // namespace kfx
+
+namespace {
+
 DevPose identity_pose() {
   DevPose p{};
   p.R[0] = p.R[4] = p.R[8] = 1.f;
@@ -87,11 +74,6 @@ constexpr int kInitialPoseCap = 1 << 16;
 
 }  // namespace
 
-// per-frame stage events: [0] start, [1] preprocess done, [2] ICP done,
-// [3] integrate done, [4] frame done, [5] local raycast done, [6] combine starts,
-// [7] / [8] a group combine's shared part (reductions, masks, resume) starts / ends
-constexpr int kStageEvents = 9;
-
 // How one frame's ICP / integrate / raycast are enqueued (frame_plan derives
 // it; enqueue_track, enqueue_map and record_icp_event follow it).
 struct FramePlan {
@@ -103,202 +85,7 @@ struct FramePlan {
   bool icp_ev_node = false;     // ... as an event-record node of the graph being captured
 };
 
-// What the last overlapped frame left for the next one (enqueue_frame_overlap
-// reads it at its start and rewrites it at its end; nothing else writes it).
-//
-// Overlapped frame k runs its preprocess on pstream into buffer set p = k & 1
-// and its ICP / integrate / raycast on the frame stream, which waits for
-// ev_prep (recorded on pstream behind the preprocess).  Frame k's pstream work
-// always starts behind ONE wait on frame k-1, the "start wait": for
-// start_sig >= sig when frame k-1's raycast signals its start (sig != 0), else
-// for ev_icp, which frame k-1 recorded behind its integrate.  Either way it
-// completes only after frame k-1's integrate has, and the frame stream is in
-// order, so after everything enqueued on the frame stream before that
-// integrate.  (DESIGN.md §13 has the measurements behind this schedule.)
-//
-//  - Buffer set p.  Its last user is frame k-2's ICP / integrate / raycast, on
-//    the frame stream before frame k-1's integrate: when `chained`, the start
-//    wait alone orders the preprocess after it, and no ev_free[p] record was
-//    or is made (each record between two frame kernels costs the frame stream
-//    2-5 us).  Otherwise the preprocess also waits for ev_free[p], which the
-//    last user of set p recorded at its end (free_rec[p]) or which is recorded
-//    now, at the frame stream's tail.
-//  - k_int_order (deep volumes: it rewrites the tile order the integrate reads)
-//    runs on pstream between the preprocess and the ev_prep record when
-//    order_pending.  The start wait orders it after frame k-1's integrate, the
-//    one that read the old order and left the intervals it sorts; ev_prep,
-//    which the frame stream waits for before frame k's ICP, orders it before
-//    the integrate that reads the new order.  Neither depends on ev_free: with
-//    the ev_free record elided the start wait is still enqueued, and it is
-//    that wait, not ev_free, that orders the cross-stream k_int_order.
-//  - `chained` holds only if the API call before this one (api_seq) enqueued
-//    frame k-1.  Any call in between (a single-stream frame into set 0, a
-//    stage hook, a group call) may have put work on the frame stream behind
-//    frame k-1's integrate that uses set p or runs an integrate, which the
-//    start wait does not cover: the chain is broken, and the ev_free[p] wait at
-//    the stream's tail orders the preprocess and k_int_order after that work.
-struct OverlapCarry {
-  bool chained = false;              // the frame provides the start wait (signal, or ev_icp behind its integrate) ...
-  unsigned long long api_seq = 0;    // ... and was enqueued by this API call
-  unsigned sig = 0;                  // the serial its raycast signals (0: it recorded ev_icp)
-  bool order_pending = false;        // its integrate left k_int_order to the next frame's pstream
-  bool free_rec[2]{};                // the last frame that used set p recorded ev_free[p]
-};
-
-struct kfx_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  kfx_intrinsics intr{};
-  kfx_params p{};
-  int L = 0;
-  LevelGeom g[kMaxLevels]{};
-  float angle_thr = 0.f;
-
-  float *raw[kMaxLevels]{};  // raw[0] = f32 mm input, raw[l] = pyrDown outputs
-  uint16_t *raw0_u16 = nullptr;
-  uint8_t *bgr = nullptr;
-  FrameView cur{}, prev{};
-  float *inv_lambda = nullptr;
-  float2 *dl0 = nullptr;  // level-0 {depth m, 1/lambda}, the integrate gather table (+ dmax shards)
-  // cur maps, dl0 and the ICP plan over them are double-buffered: with frame
-  // overlap, frame k+1's preprocess (on pstream) fills one set while frame k's
-  // ICP / integrate / raycast (on stream) read the other.  cur/dl0/icp_plan
-  // above alias set `par`, the one the last frame used.
-  FrameView curb[2]{};
-  float2 *dl0b[2]{};
-  unsigned long long *skipcnt = nullptr;  // VolView::skipcnt's three words (kfx_debug_count_settled)
-  char *itab = nullptr;  // VolView::itab's allocation (kfx_debug_int_tiles switches the view's pointer)
-  IcpPlan planb[2]{};
-  int par = 0;
-  bool overlap = true;
-  hipStream_t pstream = nullptr;
-  hipEvent_t ev_prep = nullptr, ev_free[2]{};
-  unsigned long long api_seq = 0;  // API calls into this context (counted by check_ctx)
-  hipEvent_t ev_icp = nullptr;  // after the last overlapped frame's integrate (a group member: its ICP): the next preprocess starts there
-  hipEvent_t ev_group = nullptr;  // kfx_pipeline_group combine: fork (member 0) / join (the others)
-  // raycast start signal: fine-grained word an overlapped frame's raycast
-  // stores its serial to as it starts; the next preprocess waits for it with
-  // hipStreamWaitValue32 on its own stream (null: unsupported, ev_icp instead)
-  unsigned *start_sig = nullptr;
-  unsigned sig_serial = 0;  // the last serial handed out (serials only grow: the word holds the latest one stored)
-  OverlapCarry ov;          // what the last overlapped frame left for the next one
-  bool group_chain = false;     // kfx_pipeline_group member: record ev_icp after every ICP
-  bool graphs_stale = false;    // a refused persistent ICP launch: captured graphs still hold it
-
-  // sampled kernel timing (kfx_set_kernel_timing): every `timing_every`-th
-  // pipelined frame records its stage events into the next unused set
-  int timing_every = 0;
-  unsigned long long frame_seq = 0;
-  std::vector<hipEvent_t> tsets;  // kStageEvents per sample
-  size_t tnext = 0;
-  VolView vol{};
-  DevState *st = nullptr;
-  DevPose *pose_log = nullptr;
-  int pose_cap = 0;
-  unsigned long long *icp_shards = nullptr;  // 8 x 27 int64 + ticket (self-resetting)
-  unsigned *icp_ticket = nullptr;
-  IcpSync *icp_sync = nullptr;  // persistent ICP barrier + per-iteration shard slots
-  IcpPlan icp_plan{};
-  long long icp_exact_pixels = 0;  // pixels one block may sum exactly (icp_exact_pixels of the intrinsics)
-  bool icp_persistent = false;  // plan fits and its grid is co-resident
-  bool icp_persistent_enabled = true;
-  bool icp_coop = false;  // cooperative launch of the persistent ICP (after a watchdog stall, or asked for)
-  bool icp_sharded = false;  // slab ranks: ICP partials all-reduced (kfx_set_icp_allreduce)
-  unsigned long long *counters = nullptr;
-  float *xpose = nullptr;  // explicit stage poses (21 floats: pose R,t + Rinv)
-  std::vector<void *> allocs;
-
-  float *staged_depth = nullptr;
-  uint8_t *staged_bgr = nullptr;
-  int n_staged = 0;
-
-  bool graph_mode = true;
-  bool profiling = false;
-  hipGraphExec_t graph[2] = {nullptr, nullptr};  // [u16 input], inputs in raw[0]/bgr
-  std::vector<hipGraphExec_t> staged_graph;       // one per staged frame (reads it in place)
-  // overlapped staged frames: per staged frame and buffer set p, [4i+2p] the
-  // pyrDown/preprocess graph (pstream), [4i+2p+1] the ICP/integrate/raycast graph
-  std::vector<hipGraphExec_t> ov_graph;
-  bool ov_graph_full = false;  // also capture ICP/integrate/raycast (kfx_set_graph_mode 2)
-  bool ov_main_refused = false;  // the main graph's capture failed (RCCL refused capture): eager
-  hipError_t cap_err = hipSuccess;  // the last capture's HIP error (capture_graph)
-  std::string graph_note;           // why the main graph was dropped (kfx_get_graph_note)
-  const uint8_t *last_bgr = nullptr;              // colour the last frame integrated
-  hipEvent_t ev[kStageEvents]{};  // stage events; [5]: local raycast done, [6]: combine starts (slabs)
-  float stage_ms[5]{};
-  int pending = 0;      // frames enqueued since the last host sync
-  int known_poses = 1;  // n_poses at the last sync
-  int known_fails = 0;  // DevState::fails at the last status check
-
-  // Z-slab sharding: this context owns slab `rank` of `world`
-  bool slab = false;
-  int rank = 0, world = 1;
-  uint8_t *render = nullptr;      // kfx_render output (allocated on first use)
-  // kfx_render_view: output pixels and [vmap | nmap | ts] planes (allocated on
-  // first use, grown for a larger view, freed in kfx_destroy), launch events
-  uint8_t *view_out = nullptr;
-  float *view_maps = nullptr;
-  size_t view_out_cap = 0, view_maps_cap = 0;
-  hipEvent_t ev_view[2]{};
-  float view_ms = 0.f;            // device time of the last view's launch
-  // moving volume: the pose the context was created with, the
-  // accumulated shift in voxels (p.volu_pose is derived from both), and the
-  // events around the last eviction's passes [0, 1] and the last shift [2, 3]
-  kfx_pose volu_pose0{};
-  int origin[3] = {0, 0, 0};
-  hipEvent_t ev_shift[4]{};
-  bool shift_timed[2] = {false, false};
-  // bricks out and back in: the events around the last
-  // kfx_evict_bricks [0, 1] and the last kfx_restore_bricks [2, 3]
-  hipEvent_t ev_stream[4]{};
-  bool stream_timed[2] = {false, false};
-  // world map: the uploaded records, the neighbour table's
-  // keys and entries, the count / scan workspace and the items (each grown on
-  // demand, kept, freed in kfx_destroy), and the events around the last call's
-  // table [0, 1], count + scan [1, 2] and emit [3, 4]
-  void *world_buf[5]{};
-  size_t world_cap[5]{};
-  hipEvent_t ev_world[5]{};
-  float world_ms[3]{};
-  uint8_t *mc_tab = nullptr;     // marching-cubes table (uploaded on first use)
-  // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
-  // sample index of this slab's decisive event, the first sample a bounded
-  // march left unexamined, and the hit payload
-  uint32_t *key_local = nullptr;
-  uint32_t *key_min = nullptr;    // all-reduce MIN of the [key | pend] planes over the slabs
-  int slab_bound = 0;             // kfx_set_slab_bound: 0 off (default: measured no faster), 1 on, 2 no margin
-  bool group_combine = false;     // kfx_pipeline_group member (in-process combine), this call only
-  bool pass1_bounded = false;     // the frame's slab raycast was bounded: the combine runs pass 2
-  // kfx_pipeline_async: host frames copied into a pinned ring slot, uploaded on
-  // the copy stream while earlier frames run (slot reuse ordered by events)
-  static constexpr int kRing = 4;
-  uint8_t *ring_host = nullptr, *ring_dev = nullptr;
-  uint8_t *ring_host_dev = nullptr;  // ring_host as mapped into the device address space
-  size_t ring_slot = 0;  // bytes per slot: f32 depth + BGR8
-  hipEvent_t ring_h2d[kRing]{}, ring_done[kRing]{};
-  bool ring_used[kRing]{};
-  unsigned ring_sig[kRing]{};  // the raycast start signal of the slot's last frame (0: wait ring_done)
-  hipGraphExec_t ring_graph[kRing][2][4]{};  // overlapped-frame graphs per slot and [u16 input]
-  int ring_next = 0;
-  bool ring_ready = false;  // every ring resource above created
-  struct HostReg {
-    uintptr_t host;
-    size_t bytes;
-    uint8_t *dev;  // the same pages mapped into the device address space
-  };
-  std::vector<HostReg> host_regs;  // kfx_register_host_buffer ranges
-  hipStream_t cstream = nullptr;
-  ncclComm_t comm = nullptr;      // RCCL communicator over the slab ranks (one process per GPU)
-  int *comm_chk = nullptr;        // 2 device words of the collective slab-bound check (kfx_comm_init)
-  hipEvent_t xev[5]{};            // extraction pass events (kfx_get_extract_ms)
-  int extract_passes = 0;         // the last extraction: 1 (single pass) or 2 (count + emit)
-  int extract_mode = 1;           // kfx_set_extract_passes: 1 single pass when a buffer is given, 2 always two
-  float extract_ms[3]{};          // last extraction: count pass, scan, emit pass
-  bool ext_open = false;          // kfx_slab_frame_local done, kfx_slab_frame_finish due
-  hipEvent_t *ext_pending = nullptr;  // that frame's timing sample
-};
-
-namespace {
+namespace kfx {
 
 int dalloc(kfx_ctx *c, void **p, size_t bytes) {
   hipError_t e = hipMalloc(p, bytes);
@@ -314,6 +101,10 @@ int dalloc(kfx_ctx *c, void **p, size_t bytes) {
   if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
   return KFX_OK;
 }
+
+}  // namespace kfx
+
+namespace {
 
 #ifndef KFX_COST_UPDATED
 #define KFX_COST_UPDATED 32  // slab balancing: weight of an updated voxel (64 = one visited slot; slice_cost)
@@ -998,6 +789,10 @@ int do_reset(kfx_ctx *c) {
   return KFX_OK;
 }
 
+}  // namespace
+
+namespace kfx {
+
 // The volume pose of voxel origin o: R = R0, t = t0 + R0 (o * vs),
 // from the creation pose each time, in float32 without contraction:
 // d_k = (float)o_k * vs_k, row sum (R[3i] d0 + R[3i+1] d1) + R[3i+2] d2, then
@@ -1029,7 +824,7 @@ int check_ctx(kfx_ctx *c) {
   return KFX_OK;
 }
 
-}  // namespace
+}  // namespace kfx
 
 extern "C" {
 
@@ -1837,22 +1632,19 @@ int kfx_debug_scan(kfx_ctx *c, const uint32_t *counts, int64_t n, uint64_t *offs
   if (!counts || !offsets || !total) return set_err(KFX_ERR_ARG, "null argument");
   if (n < 1 || n > (int64_t)1 << 28) return set_err(KFX_ERR_ARG, "n outside 1 .. 2^28");
   HIPCHK(hipStreamSynchronize(c->stream));
-  // the workspace of extract_items' two-pass path: counts | offsets | block sums | total
-  const size_t un = (size_t)n, nb = scan_blocks(un);
-  char *ws = nullptr;
-  HIPCHK(hipMalloc(&ws, un * 4 + un * 8 + nb * 8 + 64));
-  unsigned *dc = (unsigned *)ws;
-  unsigned long long *doff = (unsigned long long *)(ws + ((un * 4 + 7) & ~(size_t)7));
-  unsigned long long *bsum = doff + un;
-  unsigned long long *dtot = bsum + nb;
+  // the workspace of the exports' count / scan / emit passes (kfx_scanws.h)
+  const size_t un = (size_t)n;
+  void *ws = nullptr;
+  HIPCHK(hipMalloc(&ws, scanws_layout(nullptr, un).bytes));
+  const ScanWs w = scanws_layout(ws, un);
   unsigned long long ht = 0;
-  hipError_t e = hipMemcpyAsync(dc, counts, un * 4, hipMemcpyHostToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(w.counts, counts, un * 4, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
-    launch_scan(c->stream, dc, doff, bsum, un, dtot);
+    launch_scan(c->stream, w.counts, w.offsets, w.bsum, un, w.total);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(offsets, doff, un * 8, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(offsets, w.offsets, un * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&ht, w.total, 8, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(ws);
   if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("debug_scan: ") + hipGetErrorString(e));
@@ -2361,129 +2153,7 @@ int kfx_render(kfx_ctx *c, int type, uint8_t *out) {
   return KFX_OK;
 }
 
-// ---- free-viewpoint render --------------------------------
-
-// Affine3f product and rigid inverse in the float order of the device's
-// pose_mul / pose_inv (k_ray_pose; the oracle's kfo_pose_mul / kfo_pose_inv):
-// this file is built without contraction, so the host sums round the same.
-static DevPose host_pose_mul(const DevPose &a, const DevPose &b) {
-  DevPose r;
-  for (int j = 0; j < 3; ++j) {
-    for (int i = 0; i < 3; ++i) {
-      float v = 0.f;
-      for (int k = 0; k < 3; ++k) v += a.R[3 * j + k] * b.R[3 * k + i];
-      r.R[3 * j + i] = v;
-    }
-    float d = 0.f;
-    for (int k = 0; k < 3; ++k) d += a.R[3 * j + k] * b.t[k];
-    r.t[j] = d + a.t[j];
-  }
-  return r;
-}
-static DevPose host_pose_inv(const DevPose &a) {
-  DevPose r;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) r.R[3 * i + j] = a.R[3 * j + i];
-  for (int j = 0; j < 3; ++j) {
-    float d = 0.f;
-    for (int k = 0; k < 3; ++k) d += a.R[3 * k + j] * a.t[k];
-    r.t[j] = -d;
-  }
-  return r;
-}
-
-// (re)allocate one of the view's buffers for at least `bytes` (grown, never
-// shrunk; the previous view has completed: every view call ends with a sync)
-static int view_reserve(void **p, size_t *cap, size_t bytes) {
-  if (*cap >= bytes) return KFX_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return set_err(KFX_ERR_OOM, "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
-  }
-  *cap = bytes;
-  return KFX_OK;
-}
-
-int kfx_render_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_pose, int type, uint8_t *out,
-                    float *vmap, float *nmap, float *ts) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!view || !cam_pose || !out) return set_err(KFX_ERR_ARG, "null argument");
-  if (type < KFX_VIEW_PHONG || type > KFX_VIEW_COLOR) return set_err(KFX_ERR_ARG, "view type outside 0..2");
-  if (view->width < 1 || view->height < 1 || (int64_t)view->width * view->height > ((int64_t)1 << 26))
-    return set_err(KFX_ERR_ARG, "view size: width, height >= 1 and width * height <= 2^26");
-  if (!std::isfinite(view->fx) || !std::isfinite(view->fy) || view->fx == 0.f || view->fy == 0.f ||
-      !std::isfinite(view->cx) || !std::isfinite(view->cy))
-    return set_err(KFX_ERR_ARG, "view intrinsics: finite, fx and fy non-zero");
-  for (int i = 0; i < 12; ++i)
-    if (!std::isfinite(i < 9 ? cam_pose->R[i] : cam_pose->t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite view pose");
-  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "render_view on one slab of several");
-  const size_t np = (size_t)view->width * view->height;
-  const bool maps = vmap || nmap || ts;
-  if ((r = view_reserve((void **)&c->view_out, &c->view_out_cap, 3 * np))) return r;
-  if (maps && (r = view_reserve((void **)&c->view_maps, &c->view_maps_cap, 28 * np))) return r;
-  for (hipEvent_t &e : c->ev_view)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  float *dv = vmap ? c->view_maps : nullptr, *dn = nmap ? c->view_maps + 3 * np : nullptr,
-        *dt = ts ? c->view_maps + 6 * np : nullptr;
-  const DevPose cam = to_dev(*cam_pose);
-  const DevPose c2v = host_pose_mul(host_pose_inv(to_dev(c->p.volu_pose)), cam);  // tsdf_volume.cpp:59
-  const LevelGeom g = {view->width, view->height, view->fx, view->fy, view->cx, view->cy};
-  // on the frame stream, behind every queued frame's integrate; nothing the
-  // tracker reads is written, and the pending tracking status is left alone
-  HIPCHK(hipEventRecord(c->ev_view[0], c->stream));
-  launch_view(c->stream, c->vol, g, c2v, cam.t, type, c->view_out, dv, dn, dt);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_view[1], c->stream));
-  HIPCHK(hipMemcpyAsync(out, c->view_out, 3 * np, hipMemcpyDeviceToHost, c->stream));
-  if (vmap) HIPCHK(hipMemcpyAsync(vmap, dv, 12 * np, hipMemcpyDeviceToHost, c->stream));
-  if (nmap) HIPCHK(hipMemcpyAsync(nmap, dn, 12 * np, hipMemcpyDeviceToHost, c->stream));
-  if (ts) HIPCHK(hipMemcpyAsync(ts, dt, 4 * np, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipEventElapsedTime(&c->view_ms, c->ev_view[0], c->ev_view[1]));
-  return KFX_OK;
-}
-
-int kfx_get_view_ms(kfx_ctx *c, float *ms) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!ms) return set_err(KFX_ERR_ARG, "null ms");
-  *ms = c->view_ms;
-  return KFX_OK;
-}
-
-int kfx_write_ppm(const char *path, const uint8_t *bgr, int width, int height) {
-  if (!path || !bgr || width < 1 || height < 1) return set_err(KFX_ERR_ARG, "bad argument");
-  FILE *f = std::fopen(path, "wb");
-  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
-  std::fprintf(f, "P6\n%d %d\n255\n", width, height);
-  std::vector<uint8_t> row(3 * (size_t)width);
-  bool ok = true;
-  for (int y = 0; y < height && ok; ++y) {
-    const uint8_t *s = bgr + 3 * (size_t)y * width;
-    for (int x = 0; x < width; ++x) {
-      row[3 * x] = s[3 * x + 2];
-      row[3 * x + 1] = s[3 * x + 1];
-      row[3 * x + 2] = s[3 * x];
-    }
-    ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
-  }
-  ok = (std::fclose(f) == 0) && ok;
-  return ok ? KFX_OK : set_err(KFX_ERR_ARG, std::string("write failed: ") + path);
-}
-
-// ---- point cloud / PLY -----------------------------------------------------
-
-// timing events of the extraction passes (created on first use)
-static int extract_events(kfx_ctx *c) {
-  for (hipEvent_t &e : c->xev)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  return KFX_OK;
-}
+// ---- Z-slab sharding -------------------------------------------------------
 
 // The slab bound decides which collectives a frame's combine issues (the
 // [key | pend] MIN and the resume pass run only when bounded), so every rank of
@@ -2541,369 +2211,6 @@ int kfx_set_slab_bound(kfx_ctx *c, int mode) {
   c->slab_bound = mode;
   return KFX_OK;
 }
-
-int kfx_set_extract_passes(kfx_ctx *c, int passes) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (passes != 1 && passes != 2) return set_err(KFX_ERR_ARG, "extract passes are 1 or 2");
-  c->extract_mode = passes;
-  return KFX_OK;
-}
-
-int kfx_get_extract_passes(kfx_ctx *c, int *passes) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!passes) return set_err(KFX_ERR_ARG, "null out");
-  *passes = c->extract_passes;
-  return KFX_OK;
-}
-
-int kfx_get_extract_ms(kfx_ctx *c, float out_ms[3]) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!out_ms) return set_err(KFX_ERR_ARG, "null out");
-  for (int i = 0; i < 3; ++i) out_ms[i] = c->extract_ms[i];
-  return KFX_OK;
-}
-
-// Extraction into the caller's buffer with ONE read of the volume
-// (k_extract_pool: count + items into an unordered pool; the offset scan;
-// k_extract_copy: pool -> canonical order).  If the pool (cap items) cannot
-// hold every item, the counts are still complete and the emit pass of the
-// two-pass path writes the first cap items instead.  Not taken (returns 0)
-// for a count-only call (cap = 0), with kfx_set_extract_passes(2), or when
-// the buffers cannot be allocated: the caller then runs the two-pass path.
-// per = 32-bit words per item (3 per point, 9 per triangle; attributed: 7 / 21).
-constexpr int64_t kExtractPoolItems = (int64_t)1 << 23;  // single-pass pool: <= 8.4 M items (100 MB of points)
-// words per item: kfx_vertex is 7 words (kfx_extract.hip kVertexWords)
-static_assert(sizeof(kfx_vertex) == 28, "kfx_vertex is 7 32-bit words");
-static int extract_item_words(bool mesh, bool attr) { return (mesh ? 3 : 1) * (attr ? 7 : 3); }
-static int extract_single_pass(kfx_ctx *c, const uint8_t *tab, int zlo, int zhi, float *host, int64_t cap,
-                               bool attr, int64_t *total_out) {
-  const int per = extract_item_words(tab != nullptr, attr);
-  if (cap <= 0 || cap > (int64_t)1 << 36 || c->extract_mode == 2) return 0;
-  const size_t waves = extract_waves(c->vol, zlo, zhi);
-  if (waves == 0) return 0;
-  const size_t nb = scan_blocks(waves);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_off = al(waves * 4), o_bsum = o_off + al(waves * 8), o_misc = o_bsum + al(nb * 8),
-               o_at = o_misc + 256, o_list = o_at + al(waves * 8), wsb = o_list + al(waves * 4);
-  char *ws = nullptr;
-  float *pool = nullptr, *dout = nullptr;
-  // the unordered pool holds at most kExtractPoolItems items whatever the
-  // caller's cap (a larger result overflows it and takes the emit pass: the
-  // counts are complete either way); the ordered output is allocated once
-  // the count is known (n = min(total, cap) items, not cap)
-  // An attributed call's pool has the plain call's bytes, not its item count
-  // (3/7 of the items): a 2048^3 call allocates what it did before.
-  const int64_t pool_cap =
-      std::min<int64_t>(cap, kExtractPoolItems * extract_item_words(tab != nullptr, false) / per);
-  if (hipMalloc(&ws, wsb) != hipSuccess || hipMalloc(&pool, (size_t)pool_cap * per * sizeof(float)) != hipSuccess) {
-    (void)hipGetLastError();
-    if (ws) (void)hipFree(ws);
-    return 0;
-  }
-  unsigned *counts = (unsigned *)ws;
-  unsigned long long *offsets = (unsigned long long *)(ws + o_off);
-  unsigned long long *bsum = (unsigned long long *)(ws + o_bsum);
-  unsigned long long *misc = (unsigned long long *)(ws + o_misc);  // {total, ctr, overflow}
-  unsigned long long *pool_at = (unsigned long long *)(ws + o_at);
-  unsigned *list = (unsigned *)(ws + o_list);
-  const DevPose vp = to_dev(c->p.volu_pose);
-  int done = 0;
-  hipError_t e = hipMemsetAsync(misc, 0, 256, c->stream);
-  if (e == hipSuccess && extract_events(c) == KFX_OK) {
-    (void)hipEventRecord(c->xev[0], c->stream);
-    launch_extract_pool(c->stream, c->vol, vp, zlo, zhi, tab, counts, misc + 1, pool_at, list, pool,
-                        (unsigned long long)pool_cap, (unsigned *)(misc + 2), attr);
-    (void)hipEventRecord(c->xev[1], c->stream);
-    launch_scan(c->stream, counts, offsets, bsum, waves, misc);
-    (void)hipEventRecord(c->xev[2], c->stream);
-    e = hipGetLastError();
-    unsigned long long h[3] = {0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(h, misc, 24, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    const int64_t total = (int64_t)h[0], n = std::min<int64_t>(total, cap);
-    const bool ovf = (unsigned)h[2] != 0;
-    if (e == hipSuccess && n > 0) e = hipMalloc(&dout, (size_t)n * per * sizeof(float));
-    if (e == hipSuccess && n > 0) {
-      (void)hipEventRecord(c->xev[3], c->stream);
-      if (!ovf)
-        launch_extract_copy(c->stream, list, (unsigned)(h[1] >> 40), counts, pool_at, offsets, pool, dout,
-                            (unsigned long long)n, per);
-      else if (tab)
-        launch_mesh(c->stream, c->vol, vp, zlo, zhi, tab, counts, offsets, dout, (unsigned long long)n, attr);
-      else
-        launch_extract(c->stream, c->vol, vp, zlo, zhi, counts, offsets, dout, (unsigned long long)n, attr);
-      (void)hipEventRecord(c->xev[4], c->stream);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(host, dout, (size_t)n * per * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess) {
-      (void)hipEventElapsedTime(&c->extract_ms[0], c->xev[0], c->xev[1]);
-      (void)hipEventElapsedTime(&c->extract_ms[1], c->xev[1], c->xev[2]);
-      c->extract_ms[2] = 0.f;
-      if (n > 0) (void)hipEventElapsedTime(&c->extract_ms[2], c->xev[3], c->xev[4]);
-      c->extract_passes = ovf && n > 0 ? 2 : 1;
-      *total_out = total;
-      done = 1;
-    }
-  }
-  (void)hipGetLastError();
-  if (dout) (void)hipFree(dout);
-  (void)hipFree(pool);
-  (void)hipFree(ws);
-  return done;
-}
-
-static void build_mc_table(uint8_t tab[256 * 16]);
-
-// kfx_extract_points / kfx_extract_mesh and their _attr forms: `out` holds cap
-// items of extract_item_words(mesh, attr) 32-bit words.
-static int extract_items(kfx_ctx *c, bool mesh, bool attr, void *out, int64_t cap, int64_t *n_items) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, mesh ? "bad triangle buffer" : "bad point buffer");
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (mesh && !c->mc_tab) {
-    uint8_t tab[256 * 16];
-    build_mc_table(tab);
-    if ((r = dalloc(c, (void **)&c->mc_tab, sizeof(tab)))) return r;
-    HIPCHK(hipMemcpy(c->mc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-  }
-  const uint8_t *tab = mesh ? c->mc_tab : nullptr;
-  const size_t item = (size_t)extract_item_words(mesh, attr) * 4;
-  // FullScan6 visits z = 0 .. Z-2 (it reads z + 1), as do the cubes z .. z+1;
-  // a slab its owned part
-  const int zlo = std::max(0, c->vol.own0), zhi = std::min(c->vol.own1, c->vol.Z - 1);
-  const size_t waves = extract_waves(c->vol, zlo, zhi);
-  int64_t total = 0;
-  if (waves > 0 && extract_single_pass(c, tab, zlo, zhi, (float *)out, cap, attr, &total)) {
-    if (n_items) *n_items = total;
-    return KFX_OK;
-  }
-  c->extract_passes = 2;
-  if (waves > 0) {
-    const size_t nb = scan_blocks(waves);
-    char *ws = nullptr;
-    const size_t bytes = waves * 4 + waves * 8 + nb * 8 + 64;
-    HIPCHK(hipMalloc(&ws, bytes));
-    unsigned *counts = (unsigned *)ws;
-    unsigned long long *offsets = (unsigned long long *)(ws + ((waves * 4 + 7) & ~(size_t)7));
-    unsigned long long *bsum = offsets + waves;
-    unsigned long long *dtot = bsum + nb;
-    const DevPose vp = to_dev(c->p.volu_pose);
-    auto pass = [&](const unsigned long long *offs, float *dst, unsigned long long n) {
-      if (mesh)
-        launch_mesh(c->stream, c->vol, vp, zlo, zhi, tab, counts, offs, dst, n, attr);
-      else
-        launch_extract(c->stream, c->vol, vp, zlo, zhi, counts, offs, dst, n, attr);
-    };
-    if ((r = extract_events(c))) return r;
-    HIPCHK(hipEventRecord(c->xev[0], c->stream));
-    pass(nullptr, nullptr, 0);
-    HIPCHK(hipEventRecord(c->xev[1], c->stream));
-    launch_scan(c->stream, counts, offsets, bsum, waves, dtot);
-    HIPCHK(hipEventRecord(c->xev[2], c->stream));
-    unsigned long long ht = 0;
-    hipError_t e = hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    total = (int64_t)ht;
-    const int64_t n = std::min<int64_t>(total, cap);
-    float *dout = nullptr;
-    c->extract_ms[2] = 0.f;
-    if (e == hipSuccess && n > 0) {
-      e = hipMalloc(&dout, (size_t)n * item);
-      if (e == hipSuccess) {
-        (void)hipEventRecord(c->xev[3], c->stream);
-        pass(offsets, dout, (unsigned long long)n);
-        (void)hipEventRecord(c->xev[4], c->stream);
-        e = hipMemcpyAsync(out, dout, (size_t)n * item, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) (void)hipEventElapsedTime(&c->extract_ms[2], c->xev[3], c->xev[4]);
-        (void)hipFree(dout);
-      }
-    }
-    (void)hipEventElapsedTime(&c->extract_ms[0], c->xev[0], c->xev[1]);
-    (void)hipEventElapsedTime(&c->extract_ms[1], c->xev[1], c->xev[2]);
-    (void)hipFree(ws);
-    if (e != hipSuccess)
-      return set_err(KFX_ERR_HIP, std::string(mesh ? "extract_mesh: " : "extract_points: ") + hipGetErrorString(e));
-  }
-  if (n_items) *n_items = total;
-  return KFX_OK;
-}
-
-int kfx_extract_points(kfx_ctx *c, float *xyz, int64_t cap, int64_t *n_points) {
-  return extract_items(c, false, false, xyz, cap, n_points);
-}
-int kfx_extract_points_attr(kfx_ctx *c, kfx_vertex *out, int64_t cap, int64_t *n_points) {
-  return extract_items(c, false, true, out, cap, n_points);
-}
-
-// Marching-cubes triangle table, derived instead of typed in: for each of the
-// 256 inside/outside corner patterns, every cube face contributes one segment
-// per run of inside corners along its cycle (counter-clockwise seen from
-// outside), from the edge entering the run to the edge leaving it — so on an
-// ambiguous face the two inside corners are cut off separately, the same way
-// from both cubes sharing the face (no cracks).  Each cut edge then starts one
-// segment and ends one; the segments close into loops, each loop is fanned
-// from its smallest edge index.  At most 5 triangles per cube.
-static void build_mc_table(uint8_t tab[256 * 16]) {
-  int lo[12], hi[12], n = 0;
-  for (int a = 0; a < 3; ++a)
-    for (int c = 0; c < 8; ++c)
-      if (!((c >> a) & 1)) {
-        lo[n] = c;
-        hi[n] = c | (1 << a);
-        ++n;
-      }
-  auto eid = [&](int u, int v) {
-    for (int e = 0; e < 12; ++e)
-      if ((lo[e] == u && hi[e] == v) || (lo[e] == v && hi[e] == u)) return e;
-    return -1;
-  };
-  int cyc[6][4];
-  for (int a = 0, f = 0; a < 3; ++a) {
-    const int b = (a + 1) % 3, c = (a + 2) % 3;
-    static const int pb[4] = {0, 1, 1, 0}, pc[4] = {0, 0, 1, 1};
-    for (int s = 0; s < 2; ++s, ++f)
-      for (int i = 0; i < 4; ++i) {
-        const int k = s ? i : 3 - i;  // the x=0 / y=0 / z=0 face reversed: outward normal -e_a
-        cyc[f][i] = (s << a) | (pb[k] << b) | (pc[k] << c);
-      }
-  }
-  std::memset(tab, 0, 256 * 16);
-  for (int cfg = 0; cfg < 256; ++cfg) {
-    int nxt[12];
-    for (int &x : nxt) x = -1;
-    for (int f = 0; f < 6; ++f) {
-      bool ins[4];
-      for (int i = 0; i < 4; ++i) ins[i] = (cfg >> cyc[f][i]) & 1;
-      for (int i = 0; i < 4; ++i) {
-        if (!ins[i] || ins[(i + 3) % 4]) continue;  // start of a run of inside corners
-        int j = i;
-        while (ins[(j + 1) % 4]) j = (j + 1) % 4;
-        nxt[eid(cyc[f][(i + 3) % 4], cyc[f][i])] = eid(cyc[f][j], cyc[f][(j + 1) % 4]);
-      }
-    }
-    bool seen[12] = {};
-    int nt = 0;
-    for (int s = 0; s < 12; ++s) {
-      if (nxt[s] < 0 || seen[s]) continue;
-      int loop[12], m = 0;
-      for (int e = s; !seen[e]; e = nxt[e]) {
-        seen[e] = true;
-        loop[m++] = e;
-      }
-      for (int k = 1; k + 1 < m; ++k, ++nt) {
-        tab[16 * cfg + 1 + 3 * nt] = (uint8_t)loop[0];
-        tab[16 * cfg + 2 + 3 * nt] = (uint8_t)loop[k];
-        tab[16 * cfg + 3 + 3 * nt] = (uint8_t)loop[k + 1];
-      }
-    }
-    tab[16 * cfg] = (uint8_t)nt;
-  }
-}
-
-int kfx_extract_mesh(kfx_ctx *c, float *tri_xyz, int64_t cap, int64_t *n_tris) {
-  return extract_items(c, true, false, tri_xyz, cap, n_tris);
-}
-int kfx_extract_mesh_attr(kfx_ctx *c, kfx_vertex *out, int64_t cap, int64_t *n_tris) {
-  return extract_items(c, true, true, out, cap, n_tris);
-}
-
-int kfx_write_ply_mesh(const char *path, const float *tri_xyz, int64_t n) {
-  if (!path || n < 0 || (n > 0 && !tri_xyz)) return set_err(KFX_ERR_ARG, "bad argument");
-  FILE *f = std::fopen(path, "w");
-  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
-  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
-               "property float z\nelement face %lld\nproperty list uchar int vertex_indices\nend_header\n",
-               (long long)(3 * n), (long long)n);
-  for (int64_t i = 0; i < 3 * n; ++i)
-    std::fprintf(f, "%g %g %g\n", tri_xyz[3 * i], tri_xyz[3 * i + 1], tri_xyz[3 * i + 2]);
-  for (int64_t i = 0; i < n; ++i)
-    std::fprintf(f, "3 %lld %lld %lld\n", (long long)(3 * i), (long long)(3 * i + 1), (long long)(3 * i + 2));
-  std::fclose(f);
-  return KFX_OK;
-}
-
-int kfx_write_ply(const char *path, const float *xyz, int64_t n) {
-  if (!path || n < 0 || (n > 0 && !xyz)) return set_err(KFX_ERR_ARG, "bad argument");
-  FILE *f = std::fopen(path, "w");
-  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
-  // kinectfusion.cpp:154-165: ostream << float uses the default "%g" (6 digits)
-  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
-               "property float z\nend_header\n", (long long)n);
-  for (int64_t i = 0; i < n; ++i)
-    std::fprintf(f, "%g %g %g\n", xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
-  std::fclose(f);
-  return KFX_OK;
-}
-
-int kfx_save_pointcloud(kfx_ctx *c, const char *path, int64_t cap) {
-  if (!path) return set_err(KFX_ERR_ARG, "null path");
-  if (cap <= 0) cap = KFX_DEFAULT_CLOUD_POINTS;
-  int64_t total = 0;
-  int r = kfx_extract_points(c, nullptr, 0, &total);
-  if (r) return r;
-  const int64_t n = std::min(total, cap);
-  std::vector<float> pts((size_t)n * 3);
-  if (n > 0 && (r = kfx_extract_points(c, pts.data(), n, &total))) return r;
-  return kfx_write_ply(path, pts.data(), n);
-}
-
-// x y z nx ny nz red green blue per vertex (n_verts of them), after the header
-static void ply_attr_vertices(FILE *f, const kfx_vertex *v, int64_t n_verts) {
-  for (int64_t i = 0; i < n_verts; ++i)
-    std::fprintf(f, "%g %g %g %g %g %g %d %d %d\n", v[i].x, v[i].y, v[i].z, v[i].nx, v[i].ny, v[i].nz, (int)v[i].r,
-                 (int)v[i].g, (int)v[i].b);
-}
-static const char kPlyAttrProps[] =
-    "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
-    "property float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n";
-
-int kfx_write_ply_attr(const char *path, const kfx_vertex *v, int64_t n) {
-  if (!path || n < 0 || (n > 0 && !v)) return set_err(KFX_ERR_ARG, "bad argument");
-  FILE *f = std::fopen(path, "w");
-  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
-  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\n%send_header\n", (long long)n, kPlyAttrProps);
-  ply_attr_vertices(f, v, n);
-  std::fclose(f);
-  return KFX_OK;
-}
-
-int kfx_write_ply_mesh_attr(const char *path, const kfx_vertex *v, int64_t n) {
-  if (!path || n < 0 || (n > 0 && !v)) return set_err(KFX_ERR_ARG, "bad argument");
-  FILE *f = std::fopen(path, "w");
-  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
-  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\n%s"
-               "element face %lld\nproperty list uchar int vertex_indices\nend_header\n",
-               (long long)(3 * n), kPlyAttrProps, (long long)n);
-  ply_attr_vertices(f, v, 3 * n);
-  for (int64_t i = 0; i < n; ++i)
-    std::fprintf(f, "3 %lld %lld %lld\n", (long long)(3 * i), (long long)(3 * i + 1), (long long)(3 * i + 2));
-  std::fclose(f);
-  return KFX_OK;
-}
-
-// count, then extract min(total, cap) items and write them
-static int save_attr(kfx_ctx *c, const char *path, int64_t cap, bool mesh) {
-  if (!path) return set_err(KFX_ERR_ARG, "null path");
-  if (cap <= 0) cap = KFX_DEFAULT_CLOUD_POINTS;
-  int64_t total = 0;
-  int r = extract_items(c, mesh, true, nullptr, 0, &total);
-  if (r) return r;
-  const int64_t n = std::min(total, cap);
-  std::vector<kfx_vertex> v((size_t)n * (mesh ? 3 : 1));
-  if (n > 0 && (r = extract_items(c, mesh, true, v.data(), n, &total))) return r;
-  return mesh ? kfx_write_ply_mesh_attr(path, v.data(), n) : kfx_write_ply_attr(path, v.data(), n);
-}
-int kfx_save_pointcloud_attr(kfx_ctx *c, const char *path, int64_t cap) { return save_attr(c, path, cap, false); }
-int kfx_save_mesh_attr(kfx_ctx *c, const char *path, int64_t cap) { return save_attr(c, path, cap, true); }
-
-// ---- Z-slab sharding -------------------------------------------------------
 
 // slice work of a frame with the camera at cam (camera-to-world; null: the
 // first frame's identity pose)
@@ -3238,427 +2545,6 @@ int kfx_slab_frame_finish(kfx_ctx *c, const uint32_t *payload) {
   HIPCHK(hipGetLastError());
   c->pending += 1;
   return finish_frame(c);
-}
-
-// ---- moving volume -------------------------------------------
-
-// the checks kfx_shift_volume and kfx_evict_points share
-static int shift_args(kfx_ctx *c, const int shift[3]) {
-  if (!shift) return set_err(KFX_ERR_ARG, "null shift");
-  for (int k = 0; k < 3; ++k)
-    if (shift[k] % 8) return set_err(KFX_ERR_ARG, "shift components must be multiples of 8 voxels (whole bricks)");
-  if (c->slab && c->world > 1)
-    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
-  return KFX_OK;
-}
-
-int kfx_shift_volume(kfx_ctx *c, const int shift[3]) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if ((r = shift_args(c, shift))) return r;
-  if (!shift[0] && !shift[1] && !shift[2]) return KFX_OK;
-  for (hipEvent_t &e : c->ev_shift)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  // the frames queued so far run at the old pose: captured graphs hold it as
-  // a kernel argument, so they finish before the graphs are dropped
-  HIPCHK(hipStreamSynchronize(c->pstream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  // the move, and with it the state an upload of the shifted records leaves:
-  // both skip maps rebuilt from the new contents, no settled byte, the gate
-  // open
-  HIPCHK(hipEventRecord(c->ev_shift[2], c->stream));
-  launch_shift(c->stream, c->vol, shift);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_shift[3], c->stream));
-  c->shift_timed[1] = true;
-  int o[3];
-  for (int k = 0; k < 3; ++k) o[k] = c->origin[k] + shift[k];
-  set_volume_origin(c, o);
-  return KFX_OK;
-}
-
-int kfx_evict_points(kfx_ctx *c, const int shift[3], kfx_vertex *out, int64_t cap, int64_t *n) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if ((r = shift_args(c, shift))) return r;
-  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad point buffer");
-  for (hipEvent_t &e : c->ev_shift)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const size_t units = evict_units(c->vol, shift);
-  int64_t total = 0;
-  HIPCHK(hipEventRecord(c->ev_shift[0], c->stream));
-  if (units > 0) {
-    const size_t nb = scan_blocks(units);
-    char *ws = nullptr;
-    const size_t o_off = (units * 4 + 7) & ~(size_t)7;
-    HIPCHK(hipMalloc(&ws, o_off + units * 8 + nb * 8 + 64));
-    unsigned *counts = (unsigned *)ws;
-    unsigned long long *offsets = (unsigned long long *)(ws + o_off);
-    unsigned long long *bsum = offsets + units;
-    unsigned long long *dtot = bsum + nb;
-    const DevPose vp = to_dev(c->p.volu_pose);
-    launch_evict(c->stream, c->vol, vp, shift, counts, nullptr, nullptr, 0);
-    launch_scan(c->stream, counts, offsets, bsum, units, dtot);
-    unsigned long long ht = 0;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    total = (int64_t)ht;
-    const int64_t m = std::min<int64_t>(total, cap);
-    float *dout = nullptr;
-    if (e == hipSuccess && m > 0) {
-      e = hipMalloc(&dout, (size_t)m * sizeof(kfx_vertex));
-      if (e == hipSuccess) {
-        launch_evict(c->stream, c->vol, vp, shift, counts, offsets, dout, (unsigned long long)m);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(c->ev_shift[1], c->stream);
-        if (e == hipSuccess)
-          e = hipMemcpyAsync(out, dout, (size_t)m * sizeof(kfx_vertex), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(dout);
-      }
-    } else if (e == hipSuccess) {
-      e = hipEventRecord(c->ev_shift[1], c->stream);
-    }
-    (void)hipFree(ws);
-    if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("evict_points: ") + hipGetErrorString(e));
-  } else {
-    HIPCHK(hipEventRecord(c->ev_shift[1], c->stream));
-  }
-  c->shift_timed[0] = true;
-  if (n) *n = total;
-  return KFX_OK;
-}
-
-int kfx_get_volume_origin(kfx_ctx *c, int origin[3]) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!origin) return set_err(KFX_ERR_ARG, "null origin");
-  for (int k = 0; k < 3; ++k) origin[k] = c->origin[k];
-  return KFX_OK;
-}
-
-int kfx_get_volume_pose(kfx_ctx *c, kfx_pose *out) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!out) return set_err(KFX_ERR_ARG, "null pose");
-  *out = c->p.volu_pose;
-  return KFX_OK;
-}
-
-int kfx_get_shift_ms(kfx_ctx *c, float out_ms[2]) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
-  for (int k = 0; k < 2; ++k) {
-    out_ms[k] = 0.f;
-    if (!c->shift_timed[k]) continue;
-    HIPCHK(hipEventSynchronize(c->ev_shift[2 * k + 1]));
-    HIPCHK(hipEventElapsedTime(&out_ms[k], c->ev_shift[2 * k], c->ev_shift[2 * k + 1]));
-  }
-  return KFX_OK;
-}
-
-// ---- bricks out and back in ---------------------------------
-
-int kfx_evict_bricks(kfx_ctx *c, const int shift[3], kfx_brick *out, int64_t cap, int64_t *n) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if ((r = shift_args(c, shift))) return r;
-  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad brick buffer");
-  for (hipEvent_t &e : c->ev_stream)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const size_t units = brick_evict_units(c->vol, shift);
-  int64_t total = 0;
-  HIPCHK(hipEventRecord(c->ev_stream[0], c->stream));
-  if (units > 0) {
-    const size_t nb = scan_blocks(units);
-    char *ws = nullptr;
-    const size_t o_off = (units * 4 + 7) & ~(size_t)7;
-    HIPCHK(hipMalloc(&ws, o_off + units * 8 + nb * 8 + 64));
-    unsigned *counts = (unsigned *)ws;
-    unsigned long long *offsets = (unsigned long long *)(ws + o_off);
-    unsigned long long *bsum = offsets + units;
-    unsigned long long *dtot = bsum + nb;
-    launch_brick_count(c->stream, c->vol, shift, counts);
-    launch_scan(c->stream, counts, offsets, bsum, units, dtot);
-    unsigned long long ht = 0;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    total = (int64_t)ht;
-    const int64_t m = std::min<int64_t>(total, cap);
-    void *dout = nullptr;
-    if (e == hipSuccess && m > 0) {
-      e = hipMalloc(&dout, (size_t)m * sizeof(kfx_brick));
-      if (e == hipSuccess) {
-        launch_brick_emit(c->stream, c->vol, shift, c->origin, counts, offsets, dout, (unsigned long long)m);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(c->ev_stream[1], c->stream);
-        if (e == hipSuccess)
-          e = hipMemcpyAsync(out, dout, (size_t)m * sizeof(kfx_brick), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(dout);
-      }
-    } else if (e == hipSuccess) {
-      e = hipEventRecord(c->ev_stream[1], c->stream);
-    }
-    (void)hipFree(ws);
-    if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("evict_bricks: ") + hipGetErrorString(e));
-  } else {
-    HIPCHK(hipEventRecord(c->ev_stream[1], c->stream));
-  }
-  c->stream_timed[0] = true;
-  if (n) *n = total;
-  return KFX_OK;
-}
-
-int kfx_restore_bricks(kfx_ctx *c, const kfx_brick *in, int64_t n, int64_t *n_restored) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (n < 0 || (n > 0 && !in)) return set_err(KFX_ERR_ARG, "bad brick list");
-  if (c->slab && c->world > 1)
-    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
-  // the host knows the origin: the bricks that land, and no two on one brick
-  const int64_t nb[3] = {c->vol.tiles_x, c->vol.tiles_y, (c->vol.Z + 7) / 8};
-  std::vector<uint64_t> cells;
-  for (int64_t i = 0; i < n; ++i) {
-    if (in[i].reserved != 0) return set_err(KFX_ERR_ARG, "restore_bricks: a reserved field that is not 0");
-    int64_t q[3];
-    bool inside = true;
-    for (int k = 0; k < 3; ++k) {
-      q[k] = (int64_t)in[i].b[k] - c->origin[k] / 8;
-      inside = inside && q[k] >= 0 && q[k] < nb[k];
-    }
-    if (inside) cells.push_back((uint64_t)((q[2] * nb[1] + q[1]) * nb[0] + q[0]));
-  }
-  std::sort(cells.begin(), cells.end());
-  if (std::adjacent_find(cells.begin(), cells.end()) != cells.end())
-    return set_err(KFX_ERR_ARG, "restore_bricks: two bricks with the same coordinate inside the window");
-  if (n_restored) *n_restored = (int64_t)cells.size();
-  if (cells.empty()) return KFX_OK;  // no device work; the settled bytes stay
-  for (hipEvent_t &e : c->ev_stream)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  // behind every queued frame, as the shift; the captured graphs hold neither
-  // the volume's contents nor its maps and stay
-  HIPCHK(hipStreamSynchronize(c->pstream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  void *din = nullptr;
-  if (hipMalloc(&din, (size_t)n * sizeof(kfx_brick)) != hipSuccess)
-    return set_err(KFX_ERR_OOM, "restore_bricks: hipMalloc(" + std::to_string((size_t)n * sizeof(kfx_brick)) + ")");
-  hipError_t e = hipMemcpyAsync(din, in, (size_t)n * sizeof(kfx_brick), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(c->ev_stream[2], c->stream);
-  if (e == hipSuccess) {
-    launch_brick_restore(c->stream, c->vol, c->origin, din, (size_t)n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipEventRecord(c->ev_stream[3], c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(din);
-  if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("restore_bricks: ") + hipGetErrorString(e));
-  c->stream_timed[1] = true;
-  return KFX_OK;
-}
-
-int kfx_get_stream_ms(kfx_ctx *c, float out_ms[2]) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
-  for (int k = 0; k < 2; ++k) {
-    out_ms[k] = 0.f;
-    if (!c->stream_timed[k]) continue;
-    HIPCHK(hipEventSynchronize(c->ev_stream[2 * k + 1]));
-    HIPCHK(hipEventElapsedTime(&out_ms[k], c->ev_stream[2 * k], c->ev_stream[2 * k + 1]));
-  }
-  return KFX_OK;
-}
-
-// ---- world map -------------------------------------------------
-
-// the list checks kfx_world_points_attr and kfx_world_mesh_attr share
-static int world_args(kfx_ctx *c, const kfx_brick *bricks, int64_t n, const void *out, int64_t cap) {
-  if (n < 0 || (n > 0 && !bricks)) return set_err(KFX_ERR_ARG, "bad brick list");
-  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad item buffer");
-  if (c->slab && c->world > 1)
-    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
-  for (int64_t i = 0; i < n; ++i) {
-    const kfx_brick &b = bricks[i];
-    if (b.reserved != 0) return set_err(KFX_ERR_ARG, "world: a reserved field that is not 0");
-    for (int k = 0; k < 3; ++k)
-      if (b.b[k] <= -(1 << 20) || b.b[k] >= (1 << 20))
-        return set_err(KFX_ERR_ARG, "world: a brick coordinate outside (-2^20, 2^20)");
-    if (i > 0) {
-      const kfx_brick &a = bricks[i - 1];
-      const bool up = a.b[2] != b.b[2] ? a.b[2] < b.b[2] : (a.b[1] != b.b[1] ? a.b[1] < b.b[1] : a.b[0] < b.b[0]);
-      if (!up) return set_err(KFX_ERR_ARG, "world: the bricks must ascend strictly in (b[2], b[1], b[0])");
-    }
-  }
-  return KFX_OK;
-}
-
-// grow one of the world buffers to at least `bytes` (kept; the previous call
-// has completed: every world call ends with a sync)
-static int world_reserve(kfx_ctx *c, int which, size_t bytes) {
-  if (c->world_cap[which] >= bytes) return KFX_OK;
-  if (c->world_buf[which]) (void)hipFree(c->world_buf[which]);
-  c->world_buf[which] = nullptr;
-  c->world_cap[which] = 0;
-  if (hipMalloc(&c->world_buf[which], bytes) != hipSuccess) {
-    c->world_buf[which] = nullptr;
-    (void)hipGetLastError();
-    return set_err(KFX_ERR_OOM, "world: hipMalloc(" + std::to_string(bytes) + ")");
-  }
-  c->world_cap[which] = bytes;
-  return KFX_OK;
-}
-
-// kfx_world_points_attr / kfx_world_mesh_attr: `out` holds cap items of 1 / 3 kfx_vertex
-static int world_items(kfx_ctx *c, const kfx_brick *bricks, int64_t n, bool mesh, kfx_vertex *out, int64_t cap,
-                       int64_t *n_items) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if ((r = world_args(c, bricks, n, out, cap))) return r;
-  for (float &m : c->world_ms) m = 0.f;
-  if (n == 0) {  // no device work
-    if (n_items) *n_items = 0;
-    return KFX_OK;
-  }
-  if (n > ((int64_t)1 << 28)) return set_err(KFX_ERR_OOM, "world: more bricks than the record buffer can hold");
-  for (hipEvent_t &e : c->ev_world)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  if (mesh && !c->mc_tab) {
-    uint8_t tab[256 * 16];
-    build_mc_table(tab);
-    if ((r = dalloc(c, (void **)&c->mc_tab, sizeof(tab)))) return r;
-    HIPCHK(hipMemcpy(c->mc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-  }
-  const size_t nn = (size_t)n, nb = scan_blocks(nn);
-  const size_t o_off = (nn * 4 + 7) & ~(size_t)7;
-  if ((r = world_reserve(c, 0, nn * sizeof(kfx_brick))) || (r = world_reserve(c, 1, nn * 8)) ||
-      (r = world_reserve(c, 2, nn * 27 * 4)) || (r = world_reserve(c, 3, o_off + nn * 8 + nb * 8 + 64)))
-    return r;
-  unsigned long long *keys = (unsigned long long *)c->world_buf[1];
-  int32_t *neigh = (int32_t *)c->world_buf[2];
-  char *ws = (char *)c->world_buf[3];
-  unsigned *counts = (unsigned *)ws;
-  unsigned long long *offsets = (unsigned long long *)(ws + o_off);
-  unsigned long long *bsum = offsets + nn;
-  unsigned long long *dtot = bsum + nb;
-  const uint8_t *tab = mesh ? c->mc_tab : nullptr;
-  const DevPose p0 = to_dev(c->volu_pose0);  // (R0, t0): a voxel's position does not depend on where the window stands
-  hipStream_t s = c->stream;                 // behind every queued frame
-  HIPCHK(hipMemcpyAsync(c->world_buf[0], bricks, nn * sizeof(kfx_brick), hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(c->ev_world[0], s));
-  launch_world_neigh(s, c->world_buf[0], nn, keys, neigh);
-  HIPCHK(hipEventRecord(c->ev_world[1], s));
-  launch_world_sweep(s, c->world_buf[0], nn, neigh, p0, c->vol.vs, tab, counts, nullptr, nullptr, 0);
-  launch_scan(s, counts, offsets, bsum, nn, dtot);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_world[2], s));
-  unsigned long long ht = 0;
-  HIPCHK(hipMemcpyAsync(&ht, dtot, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const int64_t total = (int64_t)ht, m = std::min<int64_t>(total, cap);
-  if (m > 0) {
-    const size_t bytes = (size_t)m * (mesh ? 3 : 1) * sizeof(kfx_vertex);
-    if ((r = world_reserve(c, 4, bytes))) return r;
-    HIPCHK(hipEventRecord(c->ev_world[3], s));
-    launch_world_sweep(s, c->world_buf[0], nn, neigh, p0, c->vol.vs, tab, counts, offsets, (float *)c->world_buf[4],
-                       (unsigned long long)m);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_world[4], s));
-    HIPCHK(hipMemcpyAsync(out, c->world_buf[4], bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&c->world_ms[2], c->ev_world[3], c->ev_world[4]));
-  }
-  HIPCHK(hipEventElapsedTime(&c->world_ms[0], c->ev_world[0], c->ev_world[1]));
-  HIPCHK(hipEventElapsedTime(&c->world_ms[1], c->ev_world[1], c->ev_world[2]));
-  if (n_items) *n_items = total;
-  return KFX_OK;
-}
-
-int kfx_world_points_attr(kfx_ctx *c, const kfx_brick *bricks, int64_t n, kfx_vertex *out, int64_t cap,
-                          int64_t *n_points) {
-  return world_items(c, bricks, n, false, out, cap, n_points);
-}
-int kfx_world_mesh_attr(kfx_ctx *c, const kfx_brick *bricks, int64_t n, kfx_vertex *out, int64_t cap_tris,
-                        int64_t *n_tris) {
-  return world_items(c, bricks, n, true, out, cap_tris, n_tris);
-}
-
-int kfx_get_world_ms(kfx_ctx *c, float out_ms[3]) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
-  for (int k = 0; k < 3; ++k) out_ms[k] = c->world_ms[k];
-  return KFX_OK;
-}
-
-int kfx_world_bricks(kfx_ctx *c, const kfx_brick_store *store, kfx_brick *out, int64_t cap, int64_t *n) {
-  int r = check_ctx(c);
-  if (r) return r;
-  if (!n) return set_err(KFX_ERR_ARG, "null count");
-  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad brick buffer");
-  // the window's non-empty bricks: what a shift that drops everything evicts
-  const int all[3] = {(c->vol.X + 7) / 8 * 8, 0, 0};
-  int64_t nw = 0;
-  if ((r = kfx_evict_bricks(c, all, nullptr, 0, &nw))) return r;
-  std::vector<kfx_brick> win;
-  try {
-    win.resize((size_t)nw);
-  } catch (const std::bad_alloc &) {
-    return set_err(KFX_ERR_OOM, "world_bricks: out of memory");
-  }
-  if (nw > 0 && (r = kfx_evict_bricks(c, all, win.data(), nw, &nw))) return r;
-  *n = brick_store_merge(store, win.data(), nw, nullptr);
-  if (cap < *n) return KFX_OK;  // nothing written: size the buffer and call again
-  (void)brick_store_merge(store, win.data(), nw, out);
-  return KFX_OK;
-}
-
-int kfx_save_world_mesh(kfx_ctx *c, const kfx_brick_store *store, const char *path, int64_t cap) {
-  if (!path) return set_err(KFX_ERR_ARG, "null path");
-  if (cap <= 0) cap = KFX_DEFAULT_CLOUD_POINTS;
-  int64_t nb = 0, total = 0;
-  int r = kfx_world_bricks(c, store, nullptr, 0, &nb);
-  if (r) return r;
-  std::vector<kfx_brick> bricks;
-  std::vector<kfx_vertex> v;
-  try {
-    bricks.resize((size_t)nb);
-    if (nb > 0 && (r = kfx_world_bricks(c, store, bricks.data(), nb, &nb))) return r;
-    if ((r = kfx_world_mesh_attr(c, bricks.data(), nb, nullptr, 0, &total))) return r;
-    v.resize((size_t)std::min(total, cap) * 3);
-  } catch (const std::bad_alloc &) {
-    return set_err(KFX_ERR_OOM, "save_world_mesh: out of memory");
-  }
-  const int64_t m = std::min(total, cap);
-  if (m > 0 && (r = kfx_world_mesh_attr(c, bricks.data(), nb, v.data(), m, &total))) return r;
-  return kfx_write_ply_mesh_attr(path, v.data(), m);
-}
-
-int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *vp, const kfx_pose *cam, float ahead_m, int shift[3]) {
-  if (!p || !vp || !cam || !shift) return set_err(KFX_ERR_ARG, "null argument");
-  if (!std::isfinite(ahead_m) || ahead_m < 0.f) return set_err(KFX_ERR_ARG, "ahead_m must be finite and >= 0");
-  for (int i = 0; i < 12; ++i)
-    if (!std::isfinite(i < 9 ? vp->R[i] : vp->t[i - 9]) || !std::isfinite(i < 9 ? cam->R[i] : cam->t[i - 9]))
-      return set_err(KFX_ERR_ARG, "non-finite pose entry");
-  for (int k = 0; k < 3; ++k)
-    if (!std::isfinite(p->volu_range[k]) || p->volu_range[k] <= 0.f || p->volu_dims[k] < 1)
-      return set_err(KFX_ERR_ARG, "volume range and dims must be positive");
-  double cw[3], q[3];
-  for (int i = 0; i < 3; ++i) cw[i] = (double)cam->R[3 * i + 2] * (double)ahead_m + (double)cam->t[i];
-  for (int j = 0; j < 3; ++j) {  // q = R_v^T (c - t_v)
-    q[j] = 0.0;
-    for (int i = 0; i < 3; ++i) q[j] += (double)vp->R[3 * i + j] * (cw[i] - (double)vp->t[i]);
-  }
-  for (int k = 0; k < 3; ++k) {
-    const double vs = (double)p->volu_range[k] / (double)p->volu_dims[k];
-    shift[k] = 8 * (int)std::lround(((q[k] - (double)p->volu_range[k] / 2.0) / vs) / 8.0);
-  }
-  return KFX_OK;
 }
 
 }  // extern "C"

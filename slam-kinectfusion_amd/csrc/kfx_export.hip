@@ -1,0 +1,866 @@
+// kfx_export.hip — the host side of what reads the model out: the
+// free-viewpoint render, point cloud / mesh extraction and PLY files, the
+// moving volume, bricks out and back in, and the world map (DESIGN.md §18,
+// §20-§23).  Host code only (no __global__ function: the kernels are in
+// kfx_extract / kfx_view / kfx_shift / kfx_world.hip); no frame runs any of it.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "kfx_ctx.h"
+#include "kfx_scanws.h"
+
+namespace {
+
+int hip_err(const char *call, hipError_t e) {
+  (void)hipGetLastError();
+  return set_err(KFX_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
+}
+
+// grow a device buffer to at least `bytes` (never shrunk; nothing queued uses
+// it: every call that reserves ends with a sync)
+int reserve(void **p, size_t *cap, size_t bytes, const char *what) {
+  if (*cap >= bytes) return KFX_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) {
+    *p = nullptr;
+    (void)hipGetLastError();
+    return set_err(KFX_ERR_OOM, std::string(what) + ": hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
+  }
+  *cap = bytes;
+  return KFX_OK;
+}
+
+// a device buffer one call owns: freed on every way out of the call
+struct CallBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  CallBuf() = default;
+  CallBuf(const CallBuf &) = delete;
+  CallBuf &operator=(const CallBuf &) = delete;
+  ~CallBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+int make_events(hipEvent_t *ev, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!ev[i]) HIPCHK(hipEventCreate(&ev[i]));
+  return KFX_OK;
+}
+
+// out_ms[k] = the span ev[2k] .. ev[2k + 1] where timed[k], else 0 (kfx_get_shift_ms, kfx_get_stream_ms)
+int timed_spans(kfx_ctx *c, const hipEvent_t ev[4], const bool timed[2], float out_ms[2]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  for (int k = 0; k < 2; ++k) {
+    out_ms[k] = 0.f;
+    if (!timed[k]) continue;
+    HIPCHK(hipEventSynchronize(ev[2 * k + 1]));
+    HIPCHK(hipEventElapsedTime(&out_ms[k], ev[2 * k], ev[2 * k + 1]));
+  }
+  return KFX_OK;
+}
+
+// The export protocol: a count pass over n > 0 units, the
+// offset scan, the total to the host, then min(total, cap) items of `item`
+// bytes emitted at the scanned offsets into *items (grown to hold them: a
+// CallBuf's, or one the context keeps) and copied to `out`.
+//   count(w)              launches the pass that fills w.counts (and may fill
+//                         w.total[1], [2]) on c->stream
+//   emit(w, head, dst, m) launches the pass that writes the first m items to
+//                         dst; head = the kScanHeadWords words at w.total
+// One download and one sync when nothing is emitted (cap == 0 or total == 0),
+// else two of each.  ev: the events recorded on the way (null: none): before
+// the count, behind it, behind the scan, before the emit, and `end` behind the
+// emit, or where nothing is emitted behind the total's download.
+// *total is written once the count is known, also when a later step fails.
+struct ScanEvents {
+  hipEvent_t begin, counted, scanned, emit_begin, end;
+};
+template <class Count, class Emit>
+int count_scan_emit(kfx_ctx *c, const char *call, const ScanWs &w, size_t n, size_t item, int64_t cap, void *out,
+                    void **items, size_t *items_cap, const ScanEvents &ev, Count count, Emit emit, int64_t *total) {
+  hipStream_t s = c->stream;
+  hipError_t e = hipSuccess;
+  auto mark = [&](hipEvent_t x) {
+    if (x && e == hipSuccess) e = hipEventRecord(x, s);
+  };
+  mark(ev.begin);
+  count(w);
+  mark(ev.counted);
+  launch_scan(s, w.counts, w.offsets, w.bsum, n, w.total);
+  mark(ev.scanned);
+  if (e == hipSuccess) e = hipGetLastError();
+  unsigned long long head[kScanHeadWords] = {};
+  if (e == hipSuccess) e = hipMemcpyAsync(head, w.total, sizeof(head), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return hip_err(call, e);
+  *total = (int64_t)head[0];
+  const int64_t m = std::min<int64_t>(*total, cap);
+  if (m > 0) {
+    const int r = reserve(items, items_cap, (size_t)m * item, call);
+    if (r) return r;
+    mark(ev.emit_begin);
+    emit(w, head, *items, (unsigned long long)m);
+    if (e == hipSuccess) e = hipGetLastError();
+    mark(ev.end);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, *items, (size_t)m * item, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  } else {
+    mark(ev.end);
+  }
+  return e == hipSuccess ? KFX_OK : hip_err(call, e);
+}
+
+// the workspace of n units (+ extra bytes) in a buffer of the caller's
+int scan_workspace(void **p, size_t *cap, size_t n, size_t extra, const char *call, ScanWs *w) {
+  const int r = reserve(p, cap, scanws_layout(nullptr, n, extra).bytes, call);
+  if (!r) *w = scanws_layout(*p, n, extra);
+  return r;
+}
+
+// kfx_evict_points / kfx_evict_bricks behind their argument checks: the
+// protocol over `units` units with per-call buffers, inside the one span
+// ev[0] .. ev[1] their getter reports (recorded also when there is no unit)
+template <class Count, class Emit>
+int evict_items(kfx_ctx *c, const char *call, hipEvent_t ev[4], bool *timed, size_t units, size_t item, int64_t cap,
+                void *out, int64_t *n, Count count, Emit emit) {
+  int r = make_events(ev, 4);
+  if (r) return r;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  int64_t total = 0;
+  HIPCHK(hipEventRecord(ev[0], c->stream));
+  if (units > 0) {
+    CallBuf ws, items;
+    ScanWs w;
+    if ((r = scan_workspace(&ws.p, &ws.cap, units, 0, call, &w))) return r;
+    const ScanEvents marks = {nullptr, nullptr, nullptr, nullptr, ev[1]};
+    if ((r = count_scan_emit(c, call, w, units, item, cap, out, &items.p, &items.cap, marks, count, emit, &total)))
+      return r;
+  } else {
+    HIPCHK(hipEventRecord(ev[1], c->stream));
+  }
+  *timed = true;
+  if (n) *n = total;
+  return KFX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- free-viewpoint render --------------------------------
+
+// Affine3f product and rigid inverse in the float order of the device's
+// pose_mul / pose_inv (k_ray_pose; the oracle's kfo_pose_mul / kfo_pose_inv):
+// this file is built without contraction, so the host sums round the same.
+static DevPose host_pose_mul(const DevPose &a, const DevPose &b) {
+  DevPose r;
+  for (int j = 0; j < 3; ++j) {
+    for (int i = 0; i < 3; ++i) {
+      float v = 0.f;
+      for (int k = 0; k < 3; ++k) v += a.R[3 * j + k] * b.R[3 * k + i];
+      r.R[3 * j + i] = v;
+    }
+    float d = 0.f;
+    for (int k = 0; k < 3; ++k) d += a.R[3 * j + k] * b.t[k];
+    r.t[j] = d + a.t[j];
+  }
+  return r;
+}
+static DevPose host_pose_inv(const DevPose &a) {
+  DevPose r;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) r.R[3 * i + j] = a.R[3 * j + i];
+  for (int j = 0; j < 3; ++j) {
+    float d = 0.f;
+    for (int k = 0; k < 3; ++k) d += a.R[3 * k + j] * a.t[k];
+    r.t[j] = -d;
+  }
+  return r;
+}
+
+int kfx_render_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_pose, int type, uint8_t *out,
+                    float *vmap, float *nmap, float *ts) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!view || !cam_pose || !out) return set_err(KFX_ERR_ARG, "null argument");
+  if (type < KFX_VIEW_PHONG || type > KFX_VIEW_COLOR) return set_err(KFX_ERR_ARG, "view type outside 0..2");
+  if (view->width < 1 || view->height < 1 || (int64_t)view->width * view->height > ((int64_t)1 << 26))
+    return set_err(KFX_ERR_ARG, "view size: width, height >= 1 and width * height <= 2^26");
+  if (!std::isfinite(view->fx) || !std::isfinite(view->fy) || view->fx == 0.f || view->fy == 0.f ||
+      !std::isfinite(view->cx) || !std::isfinite(view->cy))
+    return set_err(KFX_ERR_ARG, "view intrinsics: finite, fx and fy non-zero");
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? cam_pose->R[i] : cam_pose->t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite view pose");
+  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "render_view on one slab of several");
+  const size_t np = (size_t)view->width * view->height;
+  const bool maps = vmap || nmap || ts;
+  if ((r = reserve((void **)&c->view_out, &c->view_out_cap, 3 * np, "render_view"))) return r;
+  if (maps && (r = reserve((void **)&c->view_maps, &c->view_maps_cap, 28 * np, "render_view"))) return r;
+  if ((r = make_events(c->ev_view, 2))) return r;
+  float *dv = vmap ? c->view_maps : nullptr, *dn = nmap ? c->view_maps + 3 * np : nullptr,
+        *dt = ts ? c->view_maps + 6 * np : nullptr;
+  const DevPose cam = to_dev(*cam_pose);
+  const DevPose c2v = host_pose_mul(host_pose_inv(to_dev(c->p.volu_pose)), cam);  // tsdf_volume.cpp:59
+  const LevelGeom g = {view->width, view->height, view->fx, view->fy, view->cx, view->cy};
+  // on the frame stream, behind every queued frame's integrate; nothing the
+  // tracker reads is written, and the pending tracking status is left alone
+  HIPCHK(hipEventRecord(c->ev_view[0], c->stream));
+  launch_view(c->stream, c->vol, g, c2v, cam.t, type, c->view_out, dv, dn, dt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_view[1], c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->view_out, 3 * np, hipMemcpyDeviceToHost, c->stream));
+  if (vmap) HIPCHK(hipMemcpyAsync(vmap, dv, 12 * np, hipMemcpyDeviceToHost, c->stream));
+  if (nmap) HIPCHK(hipMemcpyAsync(nmap, dn, 12 * np, hipMemcpyDeviceToHost, c->stream));
+  if (ts) HIPCHK(hipMemcpyAsync(ts, dt, 4 * np, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->view_ms, c->ev_view[0], c->ev_view[1]));
+  return KFX_OK;
+}
+
+int kfx_get_view_ms(kfx_ctx *c, float *ms) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!ms) return set_err(KFX_ERR_ARG, "null ms");
+  *ms = c->view_ms;
+  return KFX_OK;
+}
+
+int kfx_write_ppm(const char *path, const uint8_t *bgr, int width, int height) {
+  if (!path || !bgr || width < 1 || height < 1) return set_err(KFX_ERR_ARG, "bad argument");
+  FILE *f = std::fopen(path, "wb");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  std::fprintf(f, "P6\n%d %d\n255\n", width, height);
+  std::vector<uint8_t> row(3 * (size_t)width);
+  bool ok = true;
+  for (int y = 0; y < height && ok; ++y) {
+    const uint8_t *s = bgr + 3 * (size_t)y * width;
+    for (int x = 0; x < width; ++x) {
+      row[3 * x] = s[3 * x + 2];
+      row[3 * x + 1] = s[3 * x + 1];
+      row[3 * x + 2] = s[3 * x];
+    }
+    ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? KFX_OK : set_err(KFX_ERR_ARG, std::string("write failed: ") + path);
+}
+
+// ---- point cloud / PLY -----------------------------------------------------
+
+int kfx_set_extract_passes(kfx_ctx *c, int passes) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (passes != 1 && passes != 2) return set_err(KFX_ERR_ARG, "extract passes are 1 or 2");
+  c->extract_mode = passes;
+  return KFX_OK;
+}
+
+int kfx_get_extract_passes(kfx_ctx *c, int *passes) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!passes) return set_err(KFX_ERR_ARG, "null out");
+  *passes = c->extract_passes;
+  return KFX_OK;
+}
+
+int kfx_get_extract_ms(kfx_ctx *c, float out_ms[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null out");
+  for (int i = 0; i < 3; ++i) out_ms[i] = c->extract_ms[i];
+  return KFX_OK;
+}
+
+// words per item: 3 per point, 9 per triangle; attributed 7 / 21 (kfx_vertex
+// is 7 words: kfx_extract.hip kVertexWords)
+static_assert(sizeof(kfx_vertex) == 28, "kfx_vertex is 7 32-bit words");
+static int extract_item_words(bool mesh, bool attr) { return (mesh ? 3 : 1) * (attr ? 7 : 3); }
+
+// one extraction's sweep over the slices [zlo, zhi): tab = null for points,
+// the marching-cubes table for triangles
+struct ExtractSweep {
+  kfx_ctx *c;
+  const uint8_t *tab;
+  int zlo, zhi;
+  bool attr;
+  DevPose vp;
+  // offs == null: counts per wave; else the first n items to dst at offs
+  void pass(unsigned *counts, const unsigned long long *offs, float *dst, unsigned long long n) const {
+    if (tab)
+      launch_mesh(c->stream, c->vol, vp, zlo, zhi, tab, counts, offs, dst, n, attr);
+    else
+      launch_extract(c->stream, c->vol, vp, zlo, zhi, counts, offs, dst, n, attr);
+  }
+};
+
+// One extraction of up to cap items over `waves` > 0 waves, through the driver.
+// pool = false: the sweep counts, then emits (two reads of the volume).
+// pool = true: ONE read of the volume.  The count pass is k_extract_pool
+// (counts + items into an unordered pool), the emit pass k_extract_copy (pool
+// -> canonical order); if the pool cannot hold every item the counts are
+// still complete (w.total = {total, pool counter, overflow flag}) and the
+// sweep's emit pass writes the first cap items instead.
+// Sets kfx_get_extract_ms (count pass, scan, emit pass or 0 when nothing was
+// emitted) and kfx_get_extract_passes when it succeeds.
+constexpr int64_t kExtractPoolItems = (int64_t)1 << 23;  // single-pass pool: <= 8.4 M items (100 MB of points)
+static int extract_run(const ExtractSweep &sw, const char *call, size_t waves, bool pool, void *out, int64_t cap,
+                       int64_t *total) {
+  kfx_ctx *c = sw.c;
+  const int per = extract_item_words(sw.tab != nullptr, sw.attr);
+  // the unordered pool holds at most kExtractPoolItems items whatever the
+  // caller's cap (a larger result overflows it and takes the emit pass); the
+  // ordered output is allocated once the count is known (min(total, cap)
+  // items, not cap).  An attributed call's pool has the plain call's bytes,
+  // not its item count (3/7 of the items): a 2048^3 call allocates what it did before.
+  const int64_t pool_cap =
+      std::min<int64_t>(cap, kExtractPoolItems * extract_item_words(sw.tab != nullptr, false) / per);
+  // behind the scan's regions: where each wave's items lie in the pool, and the waves that have any
+  const size_t o_list = scan_align(waves * 8);
+  CallBuf ws, pl, items;
+  ScanWs w;
+  int r;
+  if ((r = scan_workspace(&ws.p, &ws.cap, waves, pool ? o_list + scan_align(waves * 4) : 0, call, &w)) ||
+      (pool && (r = reserve(&pl.p, &pl.cap, (size_t)pool_cap * per * sizeof(float), call))) ||
+      (r = make_events(c->xev, 5)))
+    return r;
+  unsigned long long *pool_at = (unsigned long long *)w.extra;
+  unsigned *list = pool ? (unsigned *)(w.extra + o_list) : nullptr;
+  if (pool) HIPCHK(hipMemsetAsync(w.total, 0, kScanAlign, c->stream));
+  bool overflow = !pool;
+  const ScanEvents marks = {c->xev[0], c->xev[1], c->xev[2], c->xev[3], c->xev[4]};
+  r = count_scan_emit(
+      c, call, w, waves, (size_t)per * sizeof(float), cap, out, &items.p, &items.cap, marks,
+      [&](const ScanWs &) {
+        if (pool)
+          launch_extract_pool(c->stream, c->vol, sw.vp, sw.zlo, sw.zhi, sw.tab, w.counts, w.total + 1, pool_at, list,
+                              (float *)pl.p, (unsigned long long)pool_cap, (unsigned *)(w.total + 2), sw.attr);
+        else
+          sw.pass(w.counts, nullptr, nullptr, 0);
+      },
+      [&](const ScanWs &, const unsigned long long *head, void *dst, unsigned long long m) {
+        if (pool) overflow = (unsigned)head[2] != 0;
+        if (!overflow)
+          launch_extract_copy(c->stream, list, (unsigned)(head[1] >> 40), w.counts, pool_at, w.offsets,
+                              (const float *)pl.p, (float *)dst, m, per);
+        else
+          sw.pass(w.counts, w.offsets, (float *)dst, m);
+      },
+      total);
+  if (r) return r;
+  (void)hipEventElapsedTime(&c->extract_ms[0], c->xev[0], c->xev[1]);
+  (void)hipEventElapsedTime(&c->extract_ms[1], c->xev[1], c->xev[2]);
+  c->extract_ms[2] = 0.f;
+  if (std::min(*total, cap) > 0) (void)hipEventElapsedTime(&c->extract_ms[2], c->xev[3], c->xev[4]);
+  c->extract_passes = overflow ? 2 : 1;
+  return KFX_OK;
+}
+
+static void build_mc_table(uint8_t tab[256 * 16]);
+
+// the marching-cubes table, uploaded on first use
+static int ensure_mc_table(kfx_ctx *c) {
+  if (c->mc_tab) return KFX_OK;
+  uint8_t tab[256 * 16];
+  build_mc_table(tab);
+  int r = dalloc(c, (void **)&c->mc_tab, sizeof(tab));
+  if (r) return r;
+  HIPCHK(hipMemcpy(c->mc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+  return KFX_OK;
+}
+
+// kfx_extract_points / kfx_extract_mesh and their _attr forms: `out` holds cap
+// items of extract_item_words(mesh, attr) 32-bit words.
+static int extract_items(kfx_ctx *c, bool mesh, bool attr, void *out, int64_t cap, int64_t *n_items) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, mesh ? "bad triangle buffer" : "bad point buffer");
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (mesh && (r = ensure_mc_table(c))) return r;
+  // FullScan6 visits z = 0 .. Z-2 (it reads z + 1), as do the cubes z .. z+1;
+  // a slab its owned part
+  const ExtractSweep sw = {c,    mesh ? c->mc_tab : nullptr, std::max(0, c->vol.own0), std::min(c->vol.own1, c->vol.Z - 1),
+                           attr, to_dev(c->p.volu_pose)};
+  const char *call = mesh ? "extract_mesh" : "extract_points";
+  const size_t waves = extract_waves(c->vol, sw.zlo, sw.zhi);
+  int64_t total = 0;
+  // one read of the volume into the caller's buffer; not for a count-only
+  // call (cap = 0) or with kfx_set_extract_passes(2), and where it fails (its
+  // buffers cannot be allocated) the two passes run instead
+  const bool single = cap > 0 && cap <= (int64_t)1 << 36 && c->extract_mode != 2;
+  if (waves == 0)
+    c->extract_passes = 2;
+  else if (!(single && extract_run(sw, call, waves, true, out, cap, &total) == KFX_OK) &&
+           (r = extract_run(sw, call, waves, false, out, cap, &total)))
+    return r;
+  if (n_items) *n_items = total;
+  return KFX_OK;
+}
+
+
+int kfx_extract_points(kfx_ctx *c, float *xyz, int64_t cap, int64_t *n_points) {
+  return extract_items(c, false, false, xyz, cap, n_points);
+}
+int kfx_extract_points_attr(kfx_ctx *c, kfx_vertex *out, int64_t cap, int64_t *n_points) {
+  return extract_items(c, false, true, out, cap, n_points);
+}
+
+// Marching-cubes triangle table, derived instead of typed in: for each of the
+// 256 inside/outside corner patterns, every cube face contributes one segment
+// per run of inside corners along its cycle (counter-clockwise seen from
+// outside), from the edge entering the run to the edge leaving it — so on an
+// ambiguous face the two inside corners are cut off separately, the same way
+// from both cubes sharing the face (no cracks).  Each cut edge then starts one
+// segment and ends one; the segments close into loops, each loop is fanned
+// from its smallest edge index.  At most 5 triangles per cube.
+static void build_mc_table(uint8_t tab[256 * 16]) {
+  int lo[12], hi[12], n = 0;
+  for (int a = 0; a < 3; ++a)
+    for (int c = 0; c < 8; ++c)
+      if (!((c >> a) & 1)) {
+        lo[n] = c;
+        hi[n] = c | (1 << a);
+        ++n;
+      }
+  auto eid = [&](int u, int v) {
+    for (int e = 0; e < 12; ++e)
+      if ((lo[e] == u && hi[e] == v) || (lo[e] == v && hi[e] == u)) return e;
+    return -1;
+  };
+  int cyc[6][4];
+  for (int a = 0, f = 0; a < 3; ++a) {
+    const int b = (a + 1) % 3, c = (a + 2) % 3;
+    static const int pb[4] = {0, 1, 1, 0}, pc[4] = {0, 0, 1, 1};
+    for (int s = 0; s < 2; ++s, ++f)
+      for (int i = 0; i < 4; ++i) {
+        const int k = s ? i : 3 - i;  // the x=0 / y=0 / z=0 face reversed: outward normal -e_a
+        cyc[f][i] = (s << a) | (pb[k] << b) | (pc[k] << c);
+      }
+  }
+  std::memset(tab, 0, 256 * 16);
+  for (int cfg = 0; cfg < 256; ++cfg) {
+    int nxt[12];
+    for (int &x : nxt) x = -1;
+    for (int f = 0; f < 6; ++f) {
+      bool ins[4];
+      for (int i = 0; i < 4; ++i) ins[i] = (cfg >> cyc[f][i]) & 1;
+      for (int i = 0; i < 4; ++i) {
+        if (!ins[i] || ins[(i + 3) % 4]) continue;  // start of a run of inside corners
+        int j = i;
+        while (ins[(j + 1) % 4]) j = (j + 1) % 4;
+        nxt[eid(cyc[f][(i + 3) % 4], cyc[f][i])] = eid(cyc[f][j], cyc[f][(j + 1) % 4]);
+      }
+    }
+    bool seen[12] = {};
+    int nt = 0;
+    for (int s = 0; s < 12; ++s) {
+      if (nxt[s] < 0 || seen[s]) continue;
+      int loop[12], m = 0;
+      for (int e = s; !seen[e]; e = nxt[e]) {
+        seen[e] = true;
+        loop[m++] = e;
+      }
+      for (int k = 1; k + 1 < m; ++k, ++nt) {
+        tab[16 * cfg + 1 + 3 * nt] = (uint8_t)loop[0];
+        tab[16 * cfg + 2 + 3 * nt] = (uint8_t)loop[k];
+        tab[16 * cfg + 3 + 3 * nt] = (uint8_t)loop[k + 1];
+      }
+    }
+    tab[16 * cfg] = (uint8_t)nt;
+  }
+}
+
+int kfx_extract_mesh(kfx_ctx *c, float *tri_xyz, int64_t cap, int64_t *n_tris) {
+  return extract_items(c, true, false, tri_xyz, cap, n_tris);
+}
+int kfx_extract_mesh_attr(kfx_ctx *c, kfx_vertex *out, int64_t cap, int64_t *n_tris) {
+  return extract_items(c, true, true, out, cap, n_tris);
+}
+
+int kfx_write_ply_mesh(const char *path, const float *tri_xyz, int64_t n) {
+  if (!path || n < 0 || (n > 0 && !tri_xyz)) return set_err(KFX_ERR_ARG, "bad argument");
+  FILE *f = std::fopen(path, "w");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
+               "property float z\nelement face %lld\nproperty list uchar int vertex_indices\nend_header\n",
+               (long long)(3 * n), (long long)n);
+  for (int64_t i = 0; i < 3 * n; ++i)
+    std::fprintf(f, "%g %g %g\n", tri_xyz[3 * i], tri_xyz[3 * i + 1], tri_xyz[3 * i + 2]);
+  for (int64_t i = 0; i < n; ++i)
+    std::fprintf(f, "3 %lld %lld %lld\n", (long long)(3 * i), (long long)(3 * i + 1), (long long)(3 * i + 2));
+  std::fclose(f);
+  return KFX_OK;
+}
+
+int kfx_write_ply(const char *path, const float *xyz, int64_t n) {
+  if (!path || n < 0 || (n > 0 && !xyz)) return set_err(KFX_ERR_ARG, "bad argument");
+  FILE *f = std::fopen(path, "w");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  // kinectfusion.cpp:154-165: ostream << float uses the default "%g" (6 digits)
+  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
+               "property float z\nend_header\n", (long long)n);
+  for (int64_t i = 0; i < n; ++i)
+    std::fprintf(f, "%g %g %g\n", xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+  std::fclose(f);
+  return KFX_OK;
+}
+
+int kfx_save_pointcloud(kfx_ctx *c, const char *path, int64_t cap) {
+  if (!path) return set_err(KFX_ERR_ARG, "null path");
+  if (cap <= 0) cap = KFX_DEFAULT_CLOUD_POINTS;
+  int64_t total = 0;
+  int r = kfx_extract_points(c, nullptr, 0, &total);
+  if (r) return r;
+  const int64_t n = std::min(total, cap);
+  std::vector<float> pts((size_t)n * 3);
+  if (n > 0 && (r = kfx_extract_points(c, pts.data(), n, &total))) return r;
+  return kfx_write_ply(path, pts.data(), n);
+}
+
+// x y z nx ny nz red green blue per vertex (n_verts of them), after the header
+static void ply_attr_vertices(FILE *f, const kfx_vertex *v, int64_t n_verts) {
+  for (int64_t i = 0; i < n_verts; ++i)
+    std::fprintf(f, "%g %g %g %g %g %g %d %d %d\n", v[i].x, v[i].y, v[i].z, v[i].nx, v[i].ny, v[i].nz, (int)v[i].r,
+                 (int)v[i].g, (int)v[i].b);
+}
+static const char kPlyAttrProps[] =
+    "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
+    "property float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n";
+
+int kfx_write_ply_attr(const char *path, const kfx_vertex *v, int64_t n) {
+  if (!path || n < 0 || (n > 0 && !v)) return set_err(KFX_ERR_ARG, "bad argument");
+  FILE *f = std::fopen(path, "w");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\n%send_header\n", (long long)n, kPlyAttrProps);
+  ply_attr_vertices(f, v, n);
+  std::fclose(f);
+  return KFX_OK;
+}
+
+int kfx_write_ply_mesh_attr(const char *path, const kfx_vertex *v, int64_t n) {
+  if (!path || n < 0 || (n > 0 && !v)) return set_err(KFX_ERR_ARG, "bad argument");
+  FILE *f = std::fopen(path, "w");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\n%s"
+               "element face %lld\nproperty list uchar int vertex_indices\nend_header\n",
+               (long long)(3 * n), kPlyAttrProps, (long long)n);
+  ply_attr_vertices(f, v, 3 * n);
+  for (int64_t i = 0; i < n; ++i)
+    std::fprintf(f, "3 %lld %lld %lld\n", (long long)(3 * i), (long long)(3 * i + 1), (long long)(3 * i + 2));
+  std::fclose(f);
+  return KFX_OK;
+}
+
+// count, then extract min(total, cap) items and write them
+static int save_attr(kfx_ctx *c, const char *path, int64_t cap, bool mesh) {
+  if (!path) return set_err(KFX_ERR_ARG, "null path");
+  if (cap <= 0) cap = KFX_DEFAULT_CLOUD_POINTS;
+  int64_t total = 0;
+  int r = extract_items(c, mesh, true, nullptr, 0, &total);
+  if (r) return r;
+  const int64_t n = std::min(total, cap);
+  std::vector<kfx_vertex> v((size_t)n * (mesh ? 3 : 1));
+  if (n > 0 && (r = extract_items(c, mesh, true, v.data(), n, &total))) return r;
+  return mesh ? kfx_write_ply_mesh_attr(path, v.data(), n) : kfx_write_ply_attr(path, v.data(), n);
+}
+int kfx_save_pointcloud_attr(kfx_ctx *c, const char *path, int64_t cap) { return save_attr(c, path, cap, false); }
+int kfx_save_mesh_attr(kfx_ctx *c, const char *path, int64_t cap) { return save_attr(c, path, cap, true); }
+
+// ---- moving volume -------------------------------------------
+
+// the checks kfx_shift_volume and kfx_evict_points share
+static int shift_args(kfx_ctx *c, const int shift[3]) {
+  if (!shift) return set_err(KFX_ERR_ARG, "null shift");
+  for (int k = 0; k < 3; ++k)
+    if (shift[k] % 8) return set_err(KFX_ERR_ARG, "shift components must be multiples of 8 voxels (whole bricks)");
+  if (c->slab && c->world > 1)
+    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
+  return KFX_OK;
+}
+
+int kfx_shift_volume(kfx_ctx *c, const int shift[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = shift_args(c, shift))) return r;
+  if (!shift[0] && !shift[1] && !shift[2]) return KFX_OK;
+  if ((r = make_events(c->ev_shift, 4))) return r;
+  // the frames queued so far run at the old pose: captured graphs hold it as
+  // a kernel argument, so they finish before the graphs are dropped
+  HIPCHK(hipStreamSynchronize(c->pstream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  // the move, and with it the state an upload of the shifted records leaves:
+  // both skip maps rebuilt from the new contents, no settled byte, the gate
+  // open
+  HIPCHK(hipEventRecord(c->ev_shift[2], c->stream));
+  launch_shift(c->stream, c->vol, shift);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_shift[3], c->stream));
+  c->shift_timed[1] = true;
+  int o[3];
+  for (int k = 0; k < 3; ++k) o[k] = c->origin[k] + shift[k];
+  set_volume_origin(c, o);
+  return KFX_OK;
+}
+
+int kfx_evict_points(kfx_ctx *c, const int shift[3], kfx_vertex *out, int64_t cap, int64_t *n) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = shift_args(c, shift))) return r;
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad point buffer");
+  const DevPose vp = to_dev(c->p.volu_pose);
+  return evict_items(
+      c, "evict_points", c->ev_shift, &c->shift_timed[0], evict_units(c->vol, shift), sizeof(kfx_vertex), cap, out, n,
+      [&](const ScanWs &w) { launch_evict(c->stream, c->vol, vp, shift, w.counts, nullptr, nullptr, 0); },
+      [&](const ScanWs &w, const unsigned long long *, void *dst, unsigned long long m) {
+        launch_evict(c->stream, c->vol, vp, shift, w.counts, w.offsets, (float *)dst, m);
+      });
+}
+
+int kfx_get_volume_origin(kfx_ctx *c, int origin[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!origin) return set_err(KFX_ERR_ARG, "null origin");
+  for (int k = 0; k < 3; ++k) origin[k] = c->origin[k];
+  return KFX_OK;
+}
+
+int kfx_get_volume_pose(kfx_ctx *c, kfx_pose *out) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out) return set_err(KFX_ERR_ARG, "null pose");
+  *out = c->p.volu_pose;
+  return KFX_OK;
+}
+
+int kfx_get_shift_ms(kfx_ctx *c, float out_ms[2]) { return timed_spans(c, c->ev_shift, c->shift_timed, out_ms); }
+
+// ---- bricks out and back in ---------------------------------
+
+int kfx_evict_bricks(kfx_ctx *c, const int shift[3], kfx_brick *out, int64_t cap, int64_t *n) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = shift_args(c, shift))) return r;
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad brick buffer");
+  return evict_items(
+      c, "evict_bricks", c->ev_stream, &c->stream_timed[0], brick_evict_units(c->vol, shift), sizeof(kfx_brick), cap, out, n,
+      [&](const ScanWs &w) { launch_brick_count(c->stream, c->vol, shift, w.counts); },
+      [&](const ScanWs &w, const unsigned long long *, void *dst, unsigned long long m) {
+        launch_brick_emit(c->stream, c->vol, shift, c->origin, w.counts, w.offsets, dst, m);
+      });
+}
+
+int kfx_restore_bricks(kfx_ctx *c, const kfx_brick *in, int64_t n, int64_t *n_restored) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (n < 0 || (n > 0 && !in)) return set_err(KFX_ERR_ARG, "bad brick list");
+  if (c->slab && c->world > 1)
+    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
+  // the host knows the origin: the bricks that land, and no two on one brick
+  const int64_t nb[3] = {c->vol.tiles_x, c->vol.tiles_y, (c->vol.Z + 7) / 8};
+  std::vector<uint64_t> cells;
+  for (int64_t i = 0; i < n; ++i) {
+    if (in[i].reserved != 0) return set_err(KFX_ERR_ARG, "restore_bricks: a reserved field that is not 0");
+    int64_t q[3];
+    bool inside = true;
+    for (int k = 0; k < 3; ++k) {
+      q[k] = (int64_t)in[i].b[k] - c->origin[k] / 8;
+      inside = inside && q[k] >= 0 && q[k] < nb[k];
+    }
+    if (inside) cells.push_back((uint64_t)((q[2] * nb[1] + q[1]) * nb[0] + q[0]));
+  }
+  std::sort(cells.begin(), cells.end());
+  if (std::adjacent_find(cells.begin(), cells.end()) != cells.end())
+    return set_err(KFX_ERR_ARG, "restore_bricks: two bricks with the same coordinate inside the window");
+  if (n_restored) *n_restored = (int64_t)cells.size();
+  if (cells.empty()) return KFX_OK;  // no device work; the settled bytes stay
+  if ((r = make_events(c->ev_stream, 4))) return r;
+  // behind every queued frame, as the shift; the captured graphs hold neither
+  // the volume's contents nor its maps and stay
+  HIPCHK(hipStreamSynchronize(c->pstream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  void *din = nullptr;
+  if (hipMalloc(&din, (size_t)n * sizeof(kfx_brick)) != hipSuccess)
+    return set_err(KFX_ERR_OOM, "restore_bricks: hipMalloc(" + std::to_string((size_t)n * sizeof(kfx_brick)) + ")");
+  hipError_t e = hipMemcpyAsync(din, in, (size_t)n * sizeof(kfx_brick), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(c->ev_stream[2], c->stream);
+  if (e == hipSuccess) {
+    launch_brick_restore(c->stream, c->vol, c->origin, din, (size_t)n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev_stream[3], c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(din);
+  if (e != hipSuccess) return set_err(KFX_ERR_HIP, std::string("restore_bricks: ") + hipGetErrorString(e));
+  c->stream_timed[1] = true;
+  return KFX_OK;
+}
+
+int kfx_get_stream_ms(kfx_ctx *c, float out_ms[2]) { return timed_spans(c, c->ev_stream, c->stream_timed, out_ms); }
+
+// ---- world map -------------------------------------------------
+
+// the list checks kfx_world_points_attr and kfx_world_mesh_attr share
+static int world_args(kfx_ctx *c, const kfx_brick *bricks, int64_t n, const void *out, int64_t cap) {
+  if (n < 0 || (n > 0 && !bricks)) return set_err(KFX_ERR_ARG, "bad brick list");
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad item buffer");
+  if (c->slab && c->world > 1)
+    return set_err(KFX_ERR_STATE, "moving volume on one slab of several (a z shift would need an exchange)");
+  for (int64_t i = 0; i < n; ++i) {
+    const kfx_brick &b = bricks[i];
+    if (b.reserved != 0) return set_err(KFX_ERR_ARG, "world: a reserved field that is not 0");
+    for (int k = 0; k < 3; ++k)
+      if (b.b[k] <= -(1 << 20) || b.b[k] >= (1 << 20))
+        return set_err(KFX_ERR_ARG, "world: a brick coordinate outside (-2^20, 2^20)");
+    if (i > 0) {
+      const kfx_brick &a = bricks[i - 1];
+      const bool up = a.b[2] != b.b[2] ? a.b[2] < b.b[2] : (a.b[1] != b.b[1] ? a.b[1] < b.b[1] : a.b[0] < b.b[0]);
+      if (!up) return set_err(KFX_ERR_ARG, "world: the bricks must ascend strictly in (b[2], b[1], b[0])");
+    }
+  }
+  return KFX_OK;
+}
+
+// kfx_world_points_attr / kfx_world_mesh_attr: `out` holds cap items of 1 / 3 kfx_vertex
+static int world_items(kfx_ctx *c, const kfx_brick *bricks, int64_t n, bool mesh, kfx_vertex *out, int64_t cap,
+                       int64_t *n_items) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = world_args(c, bricks, n, out, cap))) return r;
+  for (float &m : c->world_ms) m = 0.f;
+  if (n == 0) {  // no device work
+    if (n_items) *n_items = 0;
+    return KFX_OK;
+  }
+  if (n > ((int64_t)1 << 28)) return set_err(KFX_ERR_OOM, "world: more bricks than the record buffer can hold");
+  if ((r = make_events(c->ev_world, 5))) return r;
+  if (mesh && (r = ensure_mc_table(c))) return r;
+  // the buffers the context keeps (grown on demand; the previous call has
+  // completed): [0] records, [1] keys, [2] neighbour table, [3] scan workspace, [4] items
+  const size_t nn = (size_t)n;
+  void **buf = c->world_buf;
+  size_t *bcap = c->world_cap;
+  ScanWs w;
+  if ((r = reserve(&buf[0], &bcap[0], nn * sizeof(kfx_brick), "world")) || (r = reserve(&buf[1], &bcap[1], nn * 8, "world")) ||
+      (r = reserve(&buf[2], &bcap[2], nn * 27 * 4, "world")) || (r = scan_workspace(&buf[3], &bcap[3], nn, 0, "world", &w)))
+    return r;
+  unsigned long long *keys = (unsigned long long *)buf[1];
+  int32_t *neigh = (int32_t *)buf[2];
+  const uint8_t *tab = mesh ? c->mc_tab : nullptr;
+  const DevPose p0 = to_dev(c->volu_pose0);  // (R0, t0): a voxel's position does not depend on where the window stands
+  hipStream_t s = c->stream;                 // behind every queued frame
+  HIPCHK(hipMemcpyAsync(buf[0], bricks, nn * sizeof(kfx_brick), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(c->ev_world[0], s));
+  launch_world_neigh(s, buf[0], nn, keys, neigh);
+  // table [0, 1], count + scan [1, 2], emit [3, 4]
+  const ScanEvents marks = {c->ev_world[1], nullptr, c->ev_world[2], c->ev_world[3], c->ev_world[4]};
+  int64_t total = 0;
+  r = count_scan_emit(
+      c, "world", w, nn, (mesh ? 3 : 1) * sizeof(kfx_vertex), cap, out, &buf[4], &bcap[4], marks,
+      [&](const ScanWs &w) {
+        launch_world_sweep(s, buf[0], nn, neigh, p0, c->vol.vs, tab, w.counts, nullptr, nullptr, 0);
+      },
+      [&](const ScanWs &w, const unsigned long long *, void *dst, unsigned long long m) {
+        launch_world_sweep(s, buf[0], nn, neigh, p0, c->vol.vs, tab, w.counts, w.offsets, (float *)dst, m);
+      },
+      &total);
+  if (r) return r;
+  if (std::min(total, cap) > 0) HIPCHK(hipEventElapsedTime(&c->world_ms[2], c->ev_world[3], c->ev_world[4]));
+  HIPCHK(hipEventElapsedTime(&c->world_ms[0], c->ev_world[0], c->ev_world[1]));
+  HIPCHK(hipEventElapsedTime(&c->world_ms[1], c->ev_world[1], c->ev_world[2]));
+  if (n_items) *n_items = total;
+  return KFX_OK;
+}
+
+int kfx_world_points_attr(kfx_ctx *c, const kfx_brick *bricks, int64_t n, kfx_vertex *out, int64_t cap,
+                          int64_t *n_points) {
+  return world_items(c, bricks, n, false, out, cap, n_points);
+}
+int kfx_world_mesh_attr(kfx_ctx *c, const kfx_brick *bricks, int64_t n, kfx_vertex *out, int64_t cap_tris,
+                        int64_t *n_tris) {
+  return world_items(c, bricks, n, true, out, cap_tris, n_tris);
+}
+
+int kfx_get_world_ms(kfx_ctx *c, float out_ms[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  for (int k = 0; k < 3; ++k) out_ms[k] = c->world_ms[k];
+  return KFX_OK;
+}
+
+int kfx_world_bricks(kfx_ctx *c, const kfx_brick_store *store, kfx_brick *out, int64_t cap, int64_t *n) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!n) return set_err(KFX_ERR_ARG, "null count");
+  if (cap < 0 || (cap > 0 && !out)) return set_err(KFX_ERR_ARG, "bad brick buffer");
+  // the window's non-empty bricks: what a shift that drops everything evicts
+  const int all[3] = {(c->vol.X + 7) / 8 * 8, 0, 0};
+  int64_t nw = 0;
+  if ((r = kfx_evict_bricks(c, all, nullptr, 0, &nw))) return r;
+  std::vector<kfx_brick> win;
+  try {
+    win.resize((size_t)nw);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "world_bricks: out of memory");
+  }
+  if (nw > 0 && (r = kfx_evict_bricks(c, all, win.data(), nw, &nw))) return r;
+  *n = brick_store_merge(store, win.data(), nw, nullptr);
+  if (cap < *n) return KFX_OK;  // nothing written: size the buffer and call again
+  (void)brick_store_merge(store, win.data(), nw, out);
+  return KFX_OK;
+}
+
+int kfx_save_world_mesh(kfx_ctx *c, const kfx_brick_store *store, const char *path, int64_t cap) {
+  if (!path) return set_err(KFX_ERR_ARG, "null path");
+  if (cap <= 0) cap = KFX_DEFAULT_CLOUD_POINTS;
+  int64_t nb = 0, total = 0;
+  int r = kfx_world_bricks(c, store, nullptr, 0, &nb);
+  if (r) return r;
+  std::vector<kfx_brick> bricks;
+  std::vector<kfx_vertex> v;
+  try {
+    bricks.resize((size_t)nb);
+    if (nb > 0 && (r = kfx_world_bricks(c, store, bricks.data(), nb, &nb))) return r;
+    if ((r = kfx_world_mesh_attr(c, bricks.data(), nb, nullptr, 0, &total))) return r;
+    v.resize((size_t)std::min(total, cap) * 3);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "save_world_mesh: out of memory");
+  }
+  const int64_t m = std::min(total, cap);
+  if (m > 0 && (r = kfx_world_mesh_attr(c, bricks.data(), nb, v.data(), m, &total))) return r;
+  return kfx_write_ply_mesh_attr(path, v.data(), m);
+}
+
+int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *vp, const kfx_pose *cam, float ahead_m, int shift[3]) {
+  if (!p || !vp || !cam || !shift) return set_err(KFX_ERR_ARG, "null argument");
+  if (!std::isfinite(ahead_m) || ahead_m < 0.f) return set_err(KFX_ERR_ARG, "ahead_m must be finite and >= 0");
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? vp->R[i] : vp->t[i - 9]) || !std::isfinite(i < 9 ? cam->R[i] : cam->t[i - 9]))
+      return set_err(KFX_ERR_ARG, "non-finite pose entry");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(p->volu_range[k]) || p->volu_range[k] <= 0.f || p->volu_dims[k] < 1)
+      return set_err(KFX_ERR_ARG, "volume range and dims must be positive");
+  double cw[3], q[3];
+  for (int i = 0; i < 3; ++i) cw[i] = (double)cam->R[3 * i + 2] * (double)ahead_m + (double)cam->t[i];
+  for (int j = 0; j < 3; ++j) {  // q = R_v^T (c - t_v)
+    q[j] = 0.0;
+    for (int i = 0; i < 3; ++i) q[j] += (double)vp->R[3 * i + j] * (cw[i] - (double)vp->t[i]);
+  }
+  for (int k = 0; k < 3; ++k) {
+    const double vs = (double)p->volu_range[k] / (double)p->volu_dims[k];
+    shift[k] = 8 * (int)std::lround(((q[k] - (double)p->volu_range[k] / 2.0) / vs) / 8.0);
+  }
+  return KFX_OK;
+}
+
+}  // extern "C"

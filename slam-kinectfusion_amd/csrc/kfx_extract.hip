@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "kfx_extract_dev.h"
+#include "kfx_scanws.h"
 
 #ifndef KFX_XSWEEP_WAVES
 #define KFX_XSWEEP_WAVES 65536  // extraction: units per wave grow (up to 64) while this many waves remain
@@ -314,7 +315,6 @@ void launch_mesh(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zh
   else
     launch_xsweep<kXCount>(s, v, vpose, zlo, zhi, tab, counts, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
 }
-size_t scan_blocks(size_t n) { return (n + 4095) / 4096; }
 void launch_extract_pool(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
                          unsigned *counts, unsigned long long *ctr, unsigned long long *pool_at, unsigned *list,
                          float *pool, unsigned long long pool_cap, unsigned *overflow, bool attr) {

@@ -181,7 +181,7 @@ __device__ __forceinline__ unsigned extract_wave(const View &v, const DevPose &a
 // Marching cubes (§8 f5; C5 asks for a mesh, the reference has none).  Cube
 // (x, y, z) = the 8 voxels (x+dx, y+dy, z+dz); all 8 must have weight > 0;
 // corner c = dx | dy<<1 | dz<<2 is inside when its tsdf < 0.  `tab` (256 x
-// 16 bytes, built by the host, kfx_api.hip mc_table) lists per configuration
+// 16 bytes, built by the host, kfx_export.hip build_mc_table) lists per configuration
 // the triangles as edge indices (edge e: axis e/4, the 4 edges of an axis in
 // ascending lower-corner order).  An edge vertex interpolates the two voxel
 // centres as the point extraction does (FullScan6, tsdf_volume.cu:341-360),

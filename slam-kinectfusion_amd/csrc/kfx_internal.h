@@ -1,5 +1,5 @@
 // kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip,
-// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip) and the host runtime (kfx_api.hip).  Not part of the public ABI.
+// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip) and the host runtime (kfx_api.hip, kfx_export.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -378,7 +378,7 @@ void launch_extract(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int
 void launch_mesh(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
                  unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap,
                  bool attr = false);
-size_t scan_blocks(size_t n);  // bsum entries launch_scan needs (<= 65536)
+// (scan_blocks, the bsum entries launch_scan needs, and the layout of its workspace: kfx_scanws.h)
 // one-read extraction (k_extract_pool + scan + k_extract_copy): tab = null
 // for points, the marching-cubes table for triangles
 void launch_extract_pool(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
