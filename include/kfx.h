@@ -666,6 +666,63 @@ int kfx_brick_store_copy(const kfx_brick_store *s, kfx_brick *out, int64_t cap, 
 int kfx_world_bricks(kfx_ctx *ctx, const kfx_brick_store *store, kfx_brick *out, int64_t cap, int64_t *n);
 int kfx_save_world_mesh(kfx_ctx *ctx, const kfx_brick_store *store, const char *path, int64_t cap_tris);
 
+/* ---- indexed mesh: shared vertices and a face list ----------
+ * Added under ABI version 2, nothing else changed.  kfx_extract_mesh_attr and
+ * kfx_world_mesh_attr hand out three kfx_vertex per triangle; these hand out
+ * each surface vertex once and the triangles as indices into that list.
+ *
+ * A mesh vertex is the grid edge it lies on: the edge from voxel a to b = a +
+ * e_axis, owned by a.  Two triangle corners are the same vertex iff they lie on
+ * the same edge; vertices are never welded by position (where tsdf_b == 0,
+ * several edges give the same 28 bytes and stay distinct).  An edge is used iff
+ * (F_a < 0) != (F_b < 0) and at least one of the up to four cubes around it is
+ * complete (all 8 weights > 0, inside the volume).
+ *   verts: one kfx_vertex per used edge, the 28 bytes kfx_extract_mesh_attr
+ *     (the world form: kfx_world_mesh_attr) writes for that edge, ordered by the
+ *     owner's canonical position (z / 8, tile, z & 7, lane = 8 (y & 7) + (x & 7),
+ *     axis; in a world: brick in list order, dz, lane, axis).
+ *   tris: kfx_extract_mesh_attr's triangles in its order, three uint32_t
+ *     indices into verts each, corner order kept.
+ * So verts[tris] equals the soup call's output byte for byte, and no edge
+ * appears twice in verts.
+ *
+ * *n_verts and *n_tris are always the totals.  Both buffers are written in
+ * full iff both pointers are non-null, cap_verts >= *n_verts and cap_tris >=
+ * *n_tris; otherwise nothing is written and the call returns KFX_OK (size the
+ * buffers and call again, as kfx_brick_store_take_window: a prefix of a face
+ * list is of no use).  Null buffers with caps 0 count only.
+ * KFX_ERR_ARG: a null n_verts or n_tris, a negative cap, a null buffer with a
+ * positive cap; the world form also kfx_world_mesh_attr's list checks.
+ * KFX_ERR_STATE: a slab of a world larger than 1 (a seam's vertices would need
+ * renumbering across ranks), more than 2^32 - 1 vertices.  KFX_ERR_OOM as
+ * above.  Stream behaviour is that of the calls they stand beside: on the
+ * context's stream behind every queued frame, blocking until the data is on
+ * the host, writing nothing the tracker reads, keeping captured graphs and a
+ * pending tracking status; the world form reads only the list.
+ *
+ * kfx_get_indexed_ms: device ms of the last of the two calls (HIP events of
+ * their own; the other kfx_get_*_ms figures and these do not touch each other):
+ * [0] the world's neighbour table (0 in the window form), [1] counts + scans,
+ * [2] vertex emit, [3] index emit ([2], [3]: 0 when nothing was emitted).
+ *
+ * kfx_write_ply_mesh_indexed: ASCII PLY with kfx_write_ply_mesh_attr's vertex
+ * properties and lines, n_verts vertices, n_tris faces "3 i j k".  KFX_ERR_ARG,
+ * no file left behind: an index >= n_verts, a null pointer with a positive
+ * count, a negative count.
+ * kfx_save_mesh_indexed / kfx_save_world_mesh_indexed: one call to size, one to
+ * fill, then the writer; the world saver takes kfx_world_bricks first. */
+int kfx_extract_mesh_indexed(kfx_ctx *ctx, kfx_vertex *verts, int64_t cap_verts,
+                             uint32_t *tris, int64_t cap_tris,
+                             int64_t *n_verts, int64_t *n_tris);
+int kfx_world_mesh_indexed(kfx_ctx *ctx, const kfx_brick *bricks, int64_t n,
+                           kfx_vertex *verts, int64_t cap_verts, uint32_t *tris, int64_t cap_tris,
+                           int64_t *n_verts, int64_t *n_tris);
+int kfx_get_indexed_ms(kfx_ctx *ctx, float out_ms[4]);
+int kfx_write_ply_mesh_indexed(const char *path, const kfx_vertex *verts, int64_t n_verts,
+                               const uint32_t *tris, int64_t n_tris);
+int kfx_save_mesh_indexed(kfx_ctx *ctx, const char *path);
+int kfx_save_world_mesh_indexed(kfx_ctx *ctx, const kfx_brick_store *store, const char *path);
+
 /* ---- dataset front-end (host only; no GPU needed) --------------------------
  * depth_sensor in its DATASET build (depth_sensor.cpp:11-46 open, :186-196
  * getFrame) without OpenCV: the PNG files of `<dir>/color` and `<dir>/depth` in

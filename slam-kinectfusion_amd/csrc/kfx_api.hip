@@ -1147,6 +1147,9 @@ int kfx_destroy(kfx_ctx *c) {
     if (b) (void)hipFree(b);
   for (hipEvent_t e : c->ev_world)
     if (e) (void)hipEventDestroy(e);
+  if (c->world_tris) (void)hipFree(c->world_tris);
+  for (hipEvent_t e : c->ev_indexed)
+    if (e) (void)hipEventDestroy(e);
   for (auto &e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {c->ev_prep, c->ev_free[0], c->ev_free[1], c->ev_icp, c->ev_group})

@@ -175,6 +175,15 @@ struct kfx_ctx {
   size_t world_cap[5]{};
   hipEvent_t ev_world[5]{};
   float world_ms[3]{};
+  // indexed mesh: the world form's face list (its vertices and
+  // their keys use world_buf[4]; grown on demand, kept, freed in kfx_destroy),
+  // and the events of the last call, window or world: the table begins [0],
+  // the count [1], scans done [2], vertex emit begins [3], index emit begins
+  // [4], done [5]
+  void *world_tris = nullptr;
+  size_t world_tris_cap = 0;
+  hipEvent_t ev_indexed[6]{};
+  float indexed_ms[4]{};
   uint8_t *mc_tab = nullptr;     // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded

@@ -1,7 +1,7 @@
 // kfx_export.hip — the host side of what reads the model out: the
 // free-viewpoint render, point cloud / mesh extraction and PLY files, the
-// moving volume, bricks out and back in, and the world map (DESIGN.md §18,
-// §20-§23).  Host code only (no __global__ function: the kernels are in
+// moving volume, bricks out and back in, the world map and the indexed mesh
+// (DESIGN.md §18, §20-§24).  Host code only (no __global__ function: the kernels are in
 // kfx_extract / kfx_view / kfx_shift / kfx_world.hip); no frame runs any of it.
 #include <algorithm>
 #include <cmath>
@@ -86,39 +86,88 @@ int timed_spans(kfx_ctx *c, const hipEvent_t ev[4], const bool timed[2], float o
 struct ScanEvents {
   hipEvent_t begin, counted, scanned, emit_begin, end;
 };
-template <class Count, class Emit>
-int count_scan_emit(kfx_ctx *c, const char *call, const ScanWs &w, size_t n, size_t item, int64_t cap, void *out,
-                    void **items, size_t *items_cap, const ScanEvents &ev, Count count, Emit emit, int64_t *total) {
+// One counted quantity of an export: its workspace, the bytes of an item, the
+// caller's buffer and cap, the device buffer the items are emitted into, and
+// where the total goes.  side: device bytes per item reserved behind the m
+// emitted items (at *items + m * item) that are not copied out.
+struct ScanPart {
+  ScanWs w;
+  size_t item, side;
+  int64_t cap;
+  void *out;
+  void **items;
+  size_t *items_cap;
+  int64_t *total;
+};
+// The protocol over kParts quantities counted by one pass (the indexed mesh:
+// vertices and triangles): one scan and one total each, one emit call for all.
+//   count(part)          fills every part[i].w.counts
+//   emit(part, head, m)  writes the first m[i] items of each part to
+//                        *part[i].items; head[i] = the words at part[i].w.total.
+//                        Returns KFX_OK, or an error before it launches anything.
+// whole: every part is emitted in full when every out is non-null and every
+// total fits its cap, else nothing is (m[i] = 0 for all); without it each part
+// gets its prefix min(total, cap).
+template <int kParts, class Count, class Emit>
+int count_scan_emit_parts(kfx_ctx *c, const char *call, const ScanPart (&part)[kParts], size_t n, bool whole,
+                          const ScanEvents &ev, Count count, Emit emit) {
   hipStream_t s = c->stream;
   hipError_t e = hipSuccess;
   auto mark = [&](hipEvent_t x) {
     if (x && e == hipSuccess) e = hipEventRecord(x, s);
   };
   mark(ev.begin);
-  count(w);
+  count(part);
   mark(ev.counted);
-  launch_scan(s, w.counts, w.offsets, w.bsum, n, w.total);
+  for (const ScanPart &p : part) launch_scan(s, p.w.counts, p.w.offsets, p.w.bsum, n, p.w.total);
   mark(ev.scanned);
   if (e == hipSuccess) e = hipGetLastError();
-  unsigned long long head[kScanHeadWords] = {};
-  if (e == hipSuccess) e = hipMemcpyAsync(head, w.total, sizeof(head), hipMemcpyDeviceToHost, s);
+  unsigned long long head[kParts][kScanHeadWords] = {};
+  for (int i = 0; i < kParts; ++i)
+    if (e == hipSuccess) e = hipMemcpyAsync(head[i], part[i].w.total, sizeof(head[i]), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return hip_err(call, e);
-  *total = (int64_t)head[0];
-  const int64_t m = std::min<int64_t>(*total, cap);
-  if (m > 0) {
-    const int r = reserve(items, items_cap, (size_t)m * item, call);
-    if (r) return r;
+  unsigned long long m[kParts];
+  bool fits = true, any = false;
+  for (int i = 0; i < kParts; ++i) {
+    *part[i].total = (int64_t)head[i][0];
+    m[i] = (unsigned long long)std::min<int64_t>(*part[i].total, part[i].cap);
+    fits = fits && part[i].out && *part[i].total <= part[i].cap;
+  }
+  for (int i = 0; i < kParts; ++i) {
+    if (whole && !fits) m[i] = 0;
+    any = any || m[i] > 0;
+  }
+  if (any) {
+    for (int i = 0; i < kParts; ++i) {
+      const int r = m[i] ? reserve(part[i].items, part[i].items_cap, (size_t)m[i] * (part[i].item + part[i].side), call) : KFX_OK;
+      if (r) return r;
+    }
     mark(ev.emit_begin);
-    emit(w, head, *items, (unsigned long long)m);
+    const int r = emit(part, head, m);
+    if (r) return r;
     if (e == hipSuccess) e = hipGetLastError();
     mark(ev.end);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, *items, (size_t)m * item, hipMemcpyDeviceToHost, s);
+    for (int i = 0; i < kParts; ++i)
+      if (m[i] && e == hipSuccess)
+        e = hipMemcpyAsync(part[i].out, *part[i].items, (size_t)m[i] * part[i].item, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
   } else {
     mark(ev.end);
   }
   return e == hipSuccess ? KFX_OK : hip_err(call, e);
+}
+// one counted quantity, a prefix of min(total, cap) items (the comment above)
+template <class Count, class Emit>
+int count_scan_emit(kfx_ctx *c, const char *call, const ScanWs &w, size_t n, size_t item, int64_t cap, void *out,
+                    void **items, size_t *items_cap, const ScanEvents &ev, Count count, Emit emit, int64_t *total) {
+  const ScanPart part[1] = {{w, item, 0, cap, out, items, items_cap, total}};
+  return count_scan_emit_parts<1>(
+      c, call, part, n, false, ev, [&](const ScanPart(&p)[1]) { count(p[0].w); },
+      [&](const ScanPart(&p)[1], const unsigned long long(&head)[1][kScanHeadWords], const unsigned long long(&m)[1]) {
+        emit(p[0].w, head[0], *p[0].items, m[0]);
+        return KFX_OK;
+      });
 }
 
 // the workspace of n units (+ extra bytes) in a buffer of the caller's
@@ -152,6 +201,68 @@ int evict_items(kfx_ctx *c, const char *call, hipEvent_t ev[4], bool *timed, siz
   *timed = true;
   if (n) *n = total;
   return KFX_OK;
+}
+
+// The indexed mesh, both forms behind their checks, through the driver with two counted
+// quantities per unit: vertices (28 bytes, a 16-bit key beside each on the
+// device) and triangles (3 indices).  Both are emitted in full or not at all.
+//   pass(which, wv, wt, verts, keys, tris)  launches pass 0 (the counts), 1 (the
+//   vertices) or 2 (the indices) over the `units` units
+// ws: the two scan workspaces' buffer; vbuf / tbuf: the device items.  ev[1..5]
+// as kfx_ctx::ev_indexed; sets indexed_ms[1..3].
+template <class Pass>
+int indexed_run(kfx_ctx *c, const char *call, size_t units, void **ws, size_t *ws_cap, void **vbuf,
+                       size_t *vbuf_cap, void **tbuf, size_t *tbuf_cap, kfx_vertex *verts, int64_t cap_verts,
+                       uint32_t *tris, int64_t cap_tris, int64_t *n_verts, int64_t *n_tris, Pass pass) {
+  ScanWs wv;
+  int r = scan_workspace(ws, ws_cap, units, scanws_layout(nullptr, units).bytes, call, &wv);
+  if (r) return r;
+  const ScanWs wt = scanws_layout(wv.extra, units);  // (extra starts on a multiple of kScanAlign)
+  hipEvent_t *ev = c->ev_indexed;
+  const ScanEvents marks = {ev[1], nullptr, ev[2], ev[3], ev[5]};
+  const ScanPart part[2] = {{wv, sizeof(kfx_vertex), sizeof(uint16_t), cap_verts, verts, vbuf, vbuf_cap, n_verts},
+                            {wt, 3 * sizeof(uint32_t), 0, cap_tris, tris, tbuf, tbuf_cap, n_tris}};
+  bool emitted = false;
+  hipError_t mid = hipSuccess;
+  r = count_scan_emit_parts<2>(
+      c, call, part, units, true, marks,
+      [&](const ScanPart(&)[2]) { pass(0, wv, wt, nullptr, nullptr, nullptr); },
+      [&](const ScanPart(&)[2], const unsigned long long(&)[2][kScanHeadWords], const unsigned long long(&m)[2]) {
+        if (m[0] > 0xffffffffull) return set_err(KFX_ERR_STATE, std::string(call) + ": more than 2^32 - 1 vertices");
+        uint16_t *keys = reinterpret_cast<uint16_t *>(static_cast<char *>(*vbuf) + (size_t)m[0] * sizeof(kfx_vertex));
+        pass(1, wv, wt, *vbuf, keys, nullptr);
+        mid = hipEventRecord(ev[4], c->stream);
+        if (m[1]) pass(2, wv, wt, *vbuf, keys, static_cast<uint32_t *>(*tbuf));
+        emitted = true;
+        return (int)KFX_OK;
+      });
+  if (r) return r;
+  if (mid != hipSuccess) return hip_err(call, mid);
+  if (*n_verts > (int64_t)0xffffffffll) return set_err(KFX_ERR_STATE, std::string(call) + ": more than 2^32 - 1 vertices");
+  HIPCHK(hipEventElapsedTime(&c->indexed_ms[1], ev[1], ev[2]));
+  if (emitted) {
+    HIPCHK(hipEventElapsedTime(&c->indexed_ms[2], ev[3], ev[4]));
+    HIPCHK(hipEventElapsedTime(&c->indexed_ms[3], ev[4], ev[5]));
+  }
+  return KFX_OK;
+}
+
+// An indexed mesh to a PLY file: size, fill, write; extract(verts, cap_verts, tris, cap_tris, &nv, &nt) is one of the two calls
+template <class Extract>
+int save_indexed(const char *path, const char *call, Extract extract) {
+  int64_t nv = 0, nt = 0;
+  int r = extract(nullptr, 0, nullptr, 0, &nv, &nt);
+  if (r) return r;
+  std::vector<kfx_vertex> v;
+  std::vector<uint32_t> t;
+  try {
+    v.resize((size_t)nv);
+    t.resize((size_t)nt * 3);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, std::string(call) + ": out of memory");
+  }
+  if (nv > 0 && (r = extract(v.data(), nv, t.data(), nt, &nv, &nt))) return r;
+  return kfx_write_ply_mesh_indexed(path, v.data(), nv, t.data(), nt);
 }
 
 }  // namespace
@@ -839,6 +950,126 @@ int kfx_save_world_mesh(kfx_ctx *c, const kfx_brick_store *store, const char *pa
   const int64_t m = std::min(total, cap);
   if (m > 0 && (r = kfx_world_mesh_attr(c, bricks.data(), nb, v.data(), m, &total))) return r;
   return kfx_write_ply_mesh_attr(path, v.data(), m);
+}
+
+// ---- indexed mesh ----------------------------------------------
+
+// the buffer checks both forms share
+static int indexed_args(const kfx_vertex *verts, int64_t cap_verts, const uint32_t *tris, int64_t cap_tris,
+                        const int64_t *n_verts, const int64_t *n_tris) {
+  if (!n_verts || !n_tris) return set_err(KFX_ERR_ARG, "indexed mesh: null count");
+  if (cap_verts < 0 || (cap_verts > 0 && !verts)) return set_err(KFX_ERR_ARG, "bad vertex buffer");
+  if (cap_tris < 0 || (cap_tris > 0 && !tris)) return set_err(KFX_ERR_ARG, "bad index buffer");
+  return KFX_OK;
+}
+
+int kfx_extract_mesh_indexed(kfx_ctx *c, kfx_vertex *verts, int64_t cap_verts, uint32_t *tris, int64_t cap_tris,
+                             int64_t *n_verts, int64_t *n_tris) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = indexed_args(verts, cap_verts, tris, cap_tris, n_verts, n_tris))) return r;
+  if (c->slab && c->world > 1)
+    return set_err(KFX_ERR_STATE, "indexed mesh on one slab of several (a seam's vertices would need renumbering)");
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((r = ensure_mc_table(c)) || (r = make_events(c->ev_indexed, 6))) return r;
+  for (float &m : c->indexed_ms) m = 0.f;
+  const DevPose vp = to_dev(c->p.volu_pose);
+  CallBuf ws, vbuf, tbuf;
+  return indexed_run(c, "extract_mesh_indexed", indexed_units(c->vol), &ws.p, &ws.cap, &vbuf.p, &vbuf.cap, &tbuf.p,
+                     &tbuf.cap, verts, cap_verts, tris, cap_tris, n_verts, n_tris,
+                     [&](int which, const ScanWs &wv, const ScanWs &wt, void *dv, uint16_t *keys, uint32_t *dt) {
+                       launch_indexed(c->stream, c->vol, vp, c->mc_tab, which, wv.counts, wt.counts, wv.offsets,
+                                      wt.offsets, dv, keys, dt);
+                     });
+}
+
+int kfx_world_mesh_indexed(kfx_ctx *c, const kfx_brick *bricks, int64_t n, kfx_vertex *verts, int64_t cap_verts,
+                           uint32_t *tris, int64_t cap_tris, int64_t *n_verts, int64_t *n_tris) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = indexed_args(verts, cap_verts, tris, cap_tris, n_verts, n_tris))) return r;
+  if ((r = world_args(c, bricks, n, verts, cap_verts))) return r;
+  for (float &m : c->indexed_ms) m = 0.f;
+  if (n == 0) {  // no device work
+    *n_verts = *n_tris = 0;
+    return KFX_OK;
+  }
+  if (n > ((int64_t)1 << 28)) return set_err(KFX_ERR_OOM, "world: more bricks than the record buffer can hold");
+  if ((r = make_events(c->ev_indexed, 6)) || (r = ensure_mc_table(c))) return r;
+  // kfx_world_mesh_attr's buffers: [0] records, [1] keys, [2] neighbour table, [3] the scan workspaces,
+  // [4] vertices and their keys; the face list has its own
+  const size_t nn = (size_t)n;
+  void **buf = c->world_buf;
+  size_t *bcap = c->world_cap;
+  if ((r = reserve(&buf[0], &bcap[0], nn * sizeof(kfx_brick), "world")) || (r = reserve(&buf[1], &bcap[1], nn * 8, "world")) ||
+      (r = reserve(&buf[2], &bcap[2], nn * 27 * 4, "world")))
+    return r;
+  int32_t *neigh = (int32_t *)buf[2];
+  const DevPose p0 = to_dev(c->volu_pose0);
+  hipStream_t s = c->stream;  // behind every queued frame
+  HIPCHK(hipMemcpyAsync(buf[0], bricks, nn * sizeof(kfx_brick), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(c->ev_indexed[0], s));
+  launch_world_neigh(s, buf[0], nn, (unsigned long long *)buf[1], neigh);
+  r = indexed_run(c, "world_mesh_indexed", nn, &buf[3], &bcap[3], &buf[4], &bcap[4], &c->world_tris, &c->world_tris_cap,
+                  verts, cap_verts, tris, cap_tris, n_verts, n_tris,
+                  [&](int which, const ScanWs &wv, const ScanWs &wt, void *dv, uint16_t *keys, uint32_t *dt) {
+                    launch_world_indexed(s, buf[0], nn, neigh, p0, c->vol.vs, c->mc_tab, which, wv.counts, wt.counts,
+                                         wv.offsets, wt.offsets, dv, keys, dt);
+                  });
+  if (r) return r;
+  HIPCHK(hipEventElapsedTime(&c->indexed_ms[0], c->ev_indexed[0], c->ev_indexed[1]));
+  return KFX_OK;
+}
+
+int kfx_get_indexed_ms(kfx_ctx *c, float out_ms[4]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  for (int k = 0; k < 4; ++k) out_ms[k] = c->indexed_ms[k];
+  return KFX_OK;
+}
+
+int kfx_write_ply_mesh_indexed(const char *path, const kfx_vertex *verts, int64_t n_verts, const uint32_t *tris,
+                               int64_t n_tris) {
+  if (!path || n_verts < 0 || n_tris < 0 || (n_verts > 0 && !verts) || (n_tris > 0 && !tris))
+    return set_err(KFX_ERR_ARG, "bad argument");
+  for (int64_t i = 0; i < 3 * n_tris; ++i)  // before the file exists: none is left behind
+    if ((int64_t)tris[i] >= n_verts) return set_err(KFX_ERR_ARG, "write_ply_mesh_indexed: an index past the vertex list");
+  FILE *f = std::fopen(path, "w");
+  if (!f) return set_err(KFX_ERR_ARG, std::string("cannot open ") + path);
+  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\n%s"
+               "element face %lld\nproperty list uchar int vertex_indices\nend_header\n",
+               (long long)n_verts, kPlyAttrProps, (long long)n_tris);
+  ply_attr_vertices(f, verts, n_verts);
+  for (int64_t i = 0; i < n_tris; ++i)
+    std::fprintf(f, "3 %u %u %u\n", tris[3 * i], tris[3 * i + 1], tris[3 * i + 2]);
+  std::fclose(f);
+  return KFX_OK;
+}
+
+int kfx_save_mesh_indexed(kfx_ctx *c, const char *path) {
+  if (!path) return set_err(KFX_ERR_ARG, "null path");
+  return save_indexed(path, "save_mesh_indexed", [&](kfx_vertex *v, int64_t cv, uint32_t *t, int64_t ct, int64_t *nv, int64_t *nt) {
+    return kfx_extract_mesh_indexed(c, v, cv, t, ct, nv, nt);
+  });
+}
+
+int kfx_save_world_mesh_indexed(kfx_ctx *c, const kfx_brick_store *store, const char *path) {
+  if (!path) return set_err(KFX_ERR_ARG, "null path");
+  int64_t nb = 0;
+  int r = kfx_world_bricks(c, store, nullptr, 0, &nb);
+  if (r) return r;
+  std::vector<kfx_brick> bricks;
+  try {
+    bricks.resize((size_t)nb);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "save_world_mesh_indexed: out of memory");
+  }
+  if (nb > 0 && (r = kfx_world_bricks(c, store, bricks.data(), nb, &nb))) return r;
+  return save_indexed(path, "save_world_mesh_indexed",
+                      [&](kfx_vertex *v, int64_t cv, uint32_t *t, int64_t ct, int64_t *nv, int64_t *nt) {
+                        return kfx_world_mesh_indexed(c, bricks.data(), nb, v, cv, t, ct, nv, nt);
+                      });
 }
 
 int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *vp, const kfx_pose *cam, float ahead_m, int shift[3]) {

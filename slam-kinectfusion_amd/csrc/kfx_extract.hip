@@ -157,6 +157,68 @@ __global__ __launch_bounds__(256) void k_extract_copy(const unsigned *__restrict
   for (unsigned long long k = lane; k < n * per; k += 64) dst[k] = src[k];
 }
 
+// Indexed mesh: the sweeps of k_xsweep over the chunks of ALL
+// slices [0, Z) (the top slice owns the +x / +y edges cube z = Z - 2 uses), one
+// unit numbering for both counted quantities.  A unit's vertices are the used
+// edges its voxels own, its triangles those of its cubes (z < Z - 1).
+//   kICount: vcounts[unit], tcounts[unit]
+//   kIVerts: the vertices at voff[unit] + rank, their in-unit keys beside them
+//   kITris:  3 indices per triangle at toff[unit] + rank, each looked up by key
+//            among the vertices of the unit that owns the corner's edge
+// A clear brick bit proves both counts 0: an owned edge has a negative end at
+// the voxel or its + neighbour, which the dilated map covers as it does a
+// cube's corners.
+enum IMode { kICount = 0, kIVerts = 1, kITris = 2 };
+struct WindowFind {
+  const unsigned *__restrict__ vcounts;
+  const unsigned long long *__restrict__ voff;
+  const uint16_t *__restrict__ keys;
+  int tiles_x, ntiles;
+  __device__ __forceinline__ uint32_t operator()(int x, int y, int z, int a) const {
+    const size_t u = (size_t)(z >> 3) * ntiles + (size_t)(y >> 3) * tiles_x + (x >> 3);
+    return edge_find(keys, voff[u], vcounts[u], edge_key(x, y, z, a));
+  }
+};
+template <int kMode>
+__global__ __launch_bounds__(256) void k_isweep(VolView v, DevPose aff, const uint8_t *__restrict__ tab,
+                                                unsigned *vcounts, unsigned *tcounts,
+                                                const unsigned long long *voff, const unsigned long long *toff,
+                                                uint32_t *verts, uint16_t *keys, uint32_t *tris, int K) {
+  const int lane = threadIdx.x & 63;
+  const int ntiles = v.tiles_x * v.tiles_y;
+  const int T0 = (int)(blockIdx.x * 4 + (threadIdx.x >> 6)) * K;
+  if (T0 >= ntiles) return;
+  const int c0 = (int)blockIdx.y * kExtractZ;
+  const int zv = min(v.Z, c0 + kExtractZ), zt = min(v.Z - 1, c0 + kExtractZ);  // vertex / cube slices end here
+  const size_t ubase = (size_t)blockIdx.y * ntiles;
+  const int tl = T0 + lane;
+  const bool mine = lane < K && tl < ntiles;
+  const bool have = mine && !brick_clear(v, tl, c0);
+  if (kMode == kICount && mine && !have) vcounts[ubase + tl] = tcounts[ubase + tl] = 0u;
+  unsigned long long work = __ballot(have);
+  while (work) {  // wave-uniform
+    const int t = __ffsll((long long)work) - 1;
+    work &= work - 1ull;
+    const int tile = T0 + t;
+    const size_t unit = ubase + tile;
+    const int x = (tile % v.tiles_x) * 8 + (lane & 7);
+    const int y = (tile / v.tiles_x) * 8 + (lane >> 3);
+    if (kMode == kICount) {
+      const unsigned nv = edge_wave<false>(v, aff, x, y, c0, zv, 0ull, verts, keys);
+      const unsigned nt = mesh_wave<false>(v, aff, tab, x, y, c0, zt, 0ull, nullptr, 0ull);
+      if (lane == 0) {
+        vcounts[unit] = nv;
+        tcounts[unit] = nt;
+      }
+    } else if (kMode == kIVerts) {
+      if (vcounts[unit] != 0u) (void)edge_wave<true>(v, aff, x, y, c0, zv, voff[unit], verts, keys);
+    } else if (tcounts[unit] != 0u) {
+      const WindowFind find = {vcounts, voff, keys, v.tiles_x, ntiles};
+      index_wave(v, tab, x, y, c0, zt, toff[unit], tris, find);
+    }
+  }
+}
+
 // Exclusive scan of n u32 counts into u64 offsets (one 1024-thread block per
 // 4096 counts, then the block totals, then the fix-up); *total = the sum.
 __global__ __launch_bounds__(1024) void k_scan_local(const unsigned *in, unsigned long long *out,
@@ -330,6 +392,23 @@ void launch_extract_copy(hipStream_t s, const unsigned *list, unsigned nlist, co
   if (nlist == 0) return;
   hipLaunchKernelGGL(k_extract_copy, dim3((nlist + 3) / 4), dim3(256), 0, s, list, nlist, counts, pool_at, offsets,
                      reinterpret_cast<const uint32_t *>(pool), reinterpret_cast<uint32_t *>(out), cap, per);
+}
+size_t indexed_units(const VolView &v) { return extract_waves(v, 0, v.Z); }
+void launch_indexed(hipStream_t s, const VolView &v, DevPose vpose, const uint8_t *tab, int pass, unsigned *vcounts,
+                    unsigned *tcounts, const unsigned long long *voff, const unsigned long long *toff, void *verts,
+                    uint16_t *keys, uint32_t *tris) {
+  const int nc = extract_chunks(0, v.Z);
+  if (nc == 0) return;
+  const int tiles = v.tiles_x * v.tiles_y;
+  const int K = xsweep_units(v, 0, v.Z);
+  const dim3 grd((tiles + 4 * K - 1) / (4 * K), nc), blk(256);
+  uint32_t *vw = static_cast<uint32_t *>(verts);
+  if (pass == kICount)
+    hipLaunchKernelGGL((k_isweep<kICount>), grd, blk, 0, s, v, vpose, tab, vcounts, tcounts, voff, toff, vw, keys, tris, K);
+  else if (pass == kIVerts)
+    hipLaunchKernelGGL((k_isweep<kIVerts>), grd, blk, 0, s, v, vpose, tab, vcounts, tcounts, voff, toff, vw, keys, tris, K);
+  else
+    hipLaunchKernelGGL((k_isweep<kITris>), grd, blk, 0, s, v, vpose, tab, vcounts, tcounts, voff, toff, vw, keys, tris, K);
 }
 void launch_scan(hipStream_t s, const unsigned *counts, unsigned long long *offsets,
                  unsigned long long *bsum, size_t n, unsigned long long *total) {

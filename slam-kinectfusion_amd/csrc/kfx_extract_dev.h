@@ -269,5 +269,153 @@ __device__ __forceinline__ unsigned mesh_wave(const View &v, const DevPose &aff,
   return total;
 }
 
+// ---- indexed mesh ----------------------------------------------
+// A mesh vertex is the grid edge it lies on, owned by its lower voxel a (b = a
+// + e_axis).  The edge is used iff its ends differ in sign and one of the four
+// cubes around it (at a, a - e_j, a - e_k, a - e_j - e_k for the two other
+// axes) is complete: inside the view with all 8 weights > 0.  These are the
+// edges mesh_wave's triangles name, each once.
+// Returns the used edges of voxel (x, y, z) as a mask, bit axis.
+template <typename View>
+__device__ __forceinline__ int owned_edges(const View &v, int x, int y, int z) {
+  const auto ia = vw_index(v, x, y, z);
+  if (vw_weight(v, ia) <= 0) return 0;  // a is a corner of all four cubes
+  const bool na = vw_tsdf(v, ia) < 0;
+  const int q[3] = {x, y, z};
+  int mask = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (!vw_above(v, a, q[a])) continue;
+    const auto ib = vw_index(v, x + (a == 0), y + (a == 1), z + (a == 2));
+    if (vw_weight(v, ib) <= 0 || (vw_tsdf(v, ib) < 0) == na) continue;
+    const int j = (a + 1) % 3, k = (a + 2) % 3;
+    bool used = false;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {  // the cube at a - (s & 1) e_j - (s >> 1) e_k
+      const int sj = s & 1, sk = s >> 1;
+      if (!(sj ? vw_below(v, j, q[j]) : vw_above(v, j, q[j])) || !(sk ? vw_below(v, k, q[k]) : vw_above(v, k, q[k])))
+        continue;
+      int o[3] = {x, y, z};
+      o[j] -= sj;
+      o[k] -= sk;
+      bool all = true;
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+        all = all && vw_weight(v, vw_index(v, o[0] + (c & 1), o[1] + ((c >> 1) & 1), o[2] + ((c >> 2) & 1))) > 0;
+      used = used || all;
+    }
+    if (used) mask |= 1 << a;
+  }
+  return mask;
+}
+
+// The vertex of the edge from voxel (x, y, z) along `a`: mc_vertex<true>'s 7
+// words for that edge (the same expressions in the same order).
+template <typename View>
+__device__ __forceinline__ void edge_vertex(const View &v, const DevPose &aff, int x, int y, int z, int a,
+                                            uint32_t *dst) {
+  f3 V = {(vw_coord(v, 0, x) + 0.5f) * v.vs[0], (vw_coord(v, 1, y) + 0.5f) * v.vs[1],
+          (vw_coord(v, 2, z) + 0.5f) * v.vs[2]};
+  const float Fa = (float)vw_tsdf(v, vw_index(v, x, y, z)) * kDivShortMax;
+  const float Fb = (float)vw_tsdf(v, vw_index(v, x + (a == 0), y + (a == 1), z + (a == 2))) * kDivShortMax;
+  const float Va = a == 0 ? V.x : (a == 1 ? V.y : V.z);
+  const float Vn = Va + v.vs[a];
+  const float d_inv = 1.f / (fabsf(Fa) + fabsf(Fb));
+  const float cc = (Va * fabsf(Fb) + Vn * fabsf(Fa)) * d_inv;
+  if (a == 0) V.x = cc;
+  else if (a == 1) V.y = cc;
+  else V.z = cc;
+  const f3 p = add(rmul(aff.R, V), {aff.t[0], aff.t[1], aff.t[2]});
+  st_vertex(dst, p);
+  vertex_attr(v, aff, x, y, z, a, dst + 3);
+}
+
+// A vertex's key inside its unit (8 x 8 x 8 voxels: a window unit or a world
+// brick), < kEdgeKeys; ascends with the canonical order (z & 7, lane, axis).
+constexpr int kEdgeKeys = 8 * 64 * 3;
+__device__ __forceinline__ unsigned edge_key(int x, int y, int z, int a) {
+  return (unsigned)((((z & 7) * 64 + (y & 7) * 8 + (x & 7)) * 3) + a);
+}
+
+// One wave's unit (as extract_wave): kEmit = false returns the count of its
+// used owned edges; true also writes each one's vertex at verts[base + rank]
+// and its key at keys[base + rank], rank = the canonical order inside the unit.
+template <bool kEmit, typename View>
+__device__ __forceinline__ unsigned edge_wave(const View &v, const DevPose &aff, int x, int y, int z0, int z1,
+                                              unsigned long long base, uint32_t *verts, uint16_t *keys) {
+  const int lane = threadIdx.x & 63;
+  unsigned total = 0;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int z = z0; z < z1; ++z) {
+    const int m = owned_edges(v, x, y, z);
+    const int n = __popc((unsigned)m);
+    const unsigned long long b1 = __ballot(n >= 1), b2 = __ballot(n >= 2), b3 = __ballot(n >= 3);
+    if (kEmit) {
+      unsigned long long r = base + (unsigned long long)(__popcll(b1 & below) + __popcll(b2 & below) +
+                                                         __popcll(b3 & below));
+#pragma nounroll  // (one copy of the attribute code, as mc_vertex with its runtime axis: 3 copies take 185 VGPRs)
+      for (int a = 0; a < 3; ++a)
+        if ((m >> a) & 1) {
+          edge_vertex(v, aff, x, y, z, a, verts + (size_t)r * kVertexWords);
+          keys[r] = (uint16_t)edge_key(x, y, z, a);
+          ++r;
+        }
+    }
+    const unsigned wt = (unsigned)(__popcll(b1) + __popcll(b2) + __popcll(b3));
+    base += wt;
+    total += wt;
+  }
+  return total;
+}
+
+// The index of the vertex with key `key` among the n keys at keys[first ..]
+// (ascending); 0xFFFFFFFF when it is not there (a bug the tests catch).
+__device__ __forceinline__ uint32_t edge_find(const uint16_t *__restrict__ keys, unsigned long long first, unsigned n,
+                                              unsigned key) {
+  unsigned lo = 0, hi = n;  // first position with keys[first + position] >= key
+  while (lo < hi) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (keys[first + mid] < key) lo = mid + 1;
+    else hi = mid;
+  }
+  return (lo < n && keys[first + lo] == key) ? (uint32_t)(first + lo) : 0xffffffffu;
+}
+
+// mesh_wave's triangles of one unit as indices: tris[3 (base + rank) + corner] =
+// find(x, y, z, axis) of the corner's edge, (x, y, z) its owner voxel in the
+// view's coordinates (the cube's voxel + the edge's lower corner).
+template <typename View, typename Find>
+__device__ __forceinline__ void index_wave(const View &v, const uint8_t *__restrict__ tab, int x, int y, int z0, int z1,
+                                           unsigned long long base, uint32_t *tris, const Find &find) {
+  const int lane = threadIdx.x & 63;
+  for (int z = z0; z < z1; ++z) {
+    int cfg = 0, nt = 0;
+    if (vw_above(v, 0, x) && vw_above(v, 1, y)) {
+      bool all = true;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const auto i = vw_index(v, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1));
+        all = all && vw_weight(v, i) > 0;
+        cfg |= (vw_tsdf(v, i) < 0 ? 1 : 0) << c;
+      }
+      if (all) nt = tab[16 * cfg];
+    }
+    int incl = nt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(incl, off);
+      if (lane >= off) incl += o;
+    }
+    const unsigned long long r0 = base + (unsigned long long)(incl - nt);
+    for (int t = 0; t < 3 * nt; ++t) {
+      const int e = tab[16 * cfg + 1 + t];
+      const int a = e >> 2, k = e & 3;
+      const int c = ((k >> a) << (a + 1)) | (k & ((1 << a) - 1));  // the k-th corner (ascending) with bit a clear
+      tris[(size_t)(3 * r0 + t)] = find(x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1), a);
+    }
+    base += (unsigned)__shfl(incl, 63);
+  }
+}
+
 }  // namespace
 }  // namespace kfx

@@ -378,6 +378,15 @@ void launch_extract(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int
 void launch_mesh(hipStream_t s, const VolView &v, DevPose vpose, int zlo, int zhi, const uint8_t *tab,
                  unsigned *counts, const unsigned long long *offsets, float *out, unsigned long long cap,
                  bool attr = false);
+// indexed mesh of a whole volume.  Units = indexed_units(v): column tile x 8-slice chunk over
+// ALL slices [0, Z).  pass 0: vcounts[unit] = the used grid edges its voxels own (the mesh's vertices),
+// tcounts[unit] = launch_mesh's triangles; pass 1: the vertices (7 words) at voff[unit] + rank with their in-unit
+// keys beside them (keys[same index]); pass 2: 3 u32 vertex indices per triangle at toff[unit] + rank
+// (0xFFFFFFFF: a vertex that was not found).  xsweep_units' K, as the sweeps above.
+size_t indexed_units(const VolView &v);
+void launch_indexed(hipStream_t s, const VolView &v, DevPose vpose, const uint8_t *tab, int pass, unsigned *vcounts,
+                    unsigned *tcounts, const unsigned long long *voff, const unsigned long long *toff, void *verts,
+                    uint16_t *keys, uint32_t *tris);
 // (scan_blocks, the bsum entries launch_scan needs, and the layout of its workspace: kfx_scanws.h)
 // one-read extraction (k_extract_pool + scan + k_extract_copy): tab = null
 // for points, the marching-cubes table for triangles
@@ -446,6 +455,11 @@ void launch_world_neigh(hipStream_t s, const void *recs, size_t n, unsigned long
 void launch_world_sweep(hipStream_t s, const void *recs, size_t n, const int32_t *neigh, DevPose pose0,
                         const float vs[3], const uint8_t *tab, unsigned *counts, const unsigned long long *offsets,
                         float *out, unsigned long long cap);
+// launch_indexed's three passes on a world: units = bricks, a corner's owner looked up through neigh
+void launch_world_indexed(hipStream_t s, const void *recs, size_t n, const int32_t *neigh, DevPose pose0,
+                          const float vs[3], const uint8_t *tab, int pass, unsigned *vcounts, unsigned *tcounts,
+                          const unsigned long long *voff, const unsigned long long *toff, void *verts, uint16_t *keys,
+                          uint32_t *tris);
 
 // ---- kfx_volume_io.hip ----------------------------------------------------
 void launch_export_records(hipStream_t s, VolView v, int z0, int nz, uint64_t *dst);

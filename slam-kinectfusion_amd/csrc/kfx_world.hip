@@ -181,6 +181,65 @@ __global__ __launch_bounds__(64) void k_world_sweep(const uint4 *__restrict__ re
   if (!kEmit && lane == 0) counts[brick] = n;
 }
 
+// Indexed mesh, one block = one wave = one brick as above.
+// pass 0: vcounts[brick] = the used edges its voxels own, tcounts[brick] = its
+// triangles (both 0 without more than the gather when the tile holds nothing
+// negative: a used edge has a negative end at local 0..8); pass 1: the vertices
+// at voff[brick] + rank and their keys; pass 2: 3 indices per triangle at
+// toff[brick] + rank.  A corner's owner voxel lies at local 0..8 per axis: in
+// this brick or, through the neighbour table, one of its 7 + neighbours.
+struct WorldFind {
+  const int32_t *__restrict__ nb;  // the brick's 27 table entries
+  const unsigned *__restrict__ vcounts;
+  const unsigned long long *__restrict__ voff;
+  const uint16_t *__restrict__ keys;
+  __device__ __forceinline__ uint32_t operator()(int x, int y, int z, int a) const {
+    const int32_t r = nb[(((z >> 3) + 1) * 3 + (y >> 3) + 1) * 3 + (x >> 3) + 1];
+    if (r < 0) return 0xffffffffu;
+    return edge_find(keys, voff[r], vcounts[r], edge_key(x, y, z, a));
+  }
+};
+template <int kPass>
+__global__ __launch_bounds__(64) void k_world_isweep(const uint4 *__restrict__ recs, const int32_t *__restrict__ neigh,
+                                                     DevPose aff, WorldGeom g, const uint8_t *__restrict__ tab,
+                                                     unsigned *vcounts, unsigned *tcounts,
+                                                     const unsigned long long *__restrict__ voff,
+                                                     const unsigned long long *__restrict__ toff, uint32_t *verts,
+                                                     uint16_t *keys, uint32_t *tris) {
+  __shared__ int16_t lt[kTileVox + 1];
+  __shared__ uint32_t lc[kTileVox];
+  __shared__ uint8_t lw[kTileVox + 1];
+  const size_t brick = blockIdx.x;
+  if (kPass == 1 && vcounts[brick] == 0u) return;  // (block-uniform)
+  if (kPass == 2 && tcounts[brick] == 0u) return;
+  const int lane = threadIdx.x & 63;
+  const bool neg = world_gather(recs, neigh + brick * 27, lt, lw, lc);
+  if (kPass == 0 && !neg) {
+    if (lane == 0) vcounts[brick] = tcounts[brick] = 0u;
+    return;
+  }
+  __syncthreads();
+  const uint4 h = recs[brick * kBrickPieces];
+  WorldTile v;
+  v.tsdf = lt, v.weight = lw, v.rgb = lc;
+  v.w0[0] = 8 * (int)h.x, v.w0[1] = 8 * (int)h.y, v.w0[2] = 8 * (int)h.z;
+  for (int k = 0; k < 3; ++k) v.vs[k] = g.vs[k];
+  const int x = lane & 7, y = lane >> 3;
+  if (kPass == 0) {
+    const unsigned nv = edge_wave<false>(v, aff, x, y, 0, 8, 0ull, verts, keys);
+    const unsigned nt = mesh_wave<false, true>(v, aff, tab, x, y, 0, 8, 0ull, nullptr, 0ull);
+    if (lane == 0) {
+      vcounts[brick] = nv;
+      tcounts[brick] = nt;
+    }
+  } else if (kPass == 1) {
+    (void)edge_wave<true>(v, aff, x, y, 0, 8, voff[brick], verts, keys);
+  } else {
+    const WorldFind find = {neigh + brick * 27, vcounts, voff, keys};
+    index_wave(v, tab, x, y, 0, 8, toff[brick], tris, find);
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -209,6 +268,24 @@ void launch_world_sweep(hipStream_t s, const void *recs, size_t n, const int32_t
     hipLaunchKernelGGL((k_world_sweep<false, true>), grd, blk, 0, s, r, neigh, pose0, g, tab, counts, offsets, out, 0ull);
   else
     hipLaunchKernelGGL((k_world_sweep<false, false>), grd, blk, 0, s, r, neigh, pose0, g, tab, counts, offsets, out, 0ull);
+}
+
+void launch_world_indexed(hipStream_t s, const void *recs, size_t n, const int32_t *neigh, DevPose pose0,
+                          const float vs[3], const uint8_t *tab, int pass, unsigned *vcounts, unsigned *tcounts,
+                          const unsigned long long *voff, const unsigned long long *toff, void *verts, uint16_t *keys,
+                          uint32_t *tris) {
+  if (n == 0) return;
+  WorldGeom g;
+  for (int k = 0; k < 3; ++k) g.vs[k] = vs[k];
+  const uint4 *r = static_cast<const uint4 *>(recs);
+  uint32_t *vw = static_cast<uint32_t *>(verts);
+  const dim3 grd((unsigned)n), blk(64);
+  if (pass == 0)
+    hipLaunchKernelGGL((k_world_isweep<0>), grd, blk, 0, s, r, neigh, pose0, g, tab, vcounts, tcounts, voff, toff, vw, keys, tris);
+  else if (pass == 1)
+    hipLaunchKernelGGL((k_world_isweep<1>), grd, blk, 0, s, r, neigh, pose0, g, tab, vcounts, tcounts, voff, toff, vw, keys, tris);
+  else
+    hipLaunchKernelGGL((k_world_isweep<2>), grd, blk, 0, s, r, neigh, pose0, g, tab, vcounts, tcounts, voff, toff, vw, keys, tris);
 }
 
 }  // namespace kfx

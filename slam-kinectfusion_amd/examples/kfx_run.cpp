@@ -14,9 +14,12 @@
 // final window: a surface that left and returned appears once per departure;
 // a ninth argument, with the eighth, writes the world mesh at the end, DESIGN.md
 // §22: the window's bricks merged with the store's, kfx_save_world_mesh, every
-// surface once wherever the window stands).
+// surface once wherever the window stands; a tenth argument writes the window's
+// indexed mesh, DESIGN.md §24: shared vertices and a face list,
+// kfx_save_mesh_indexed; an eleventh, with the eighth, the world's,
+// kfx_save_world_mesh_indexed).
 //   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
-//                  [followed_cloud.ply] [stream] [world_mesh.ply]
+//                  [followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply]
 #include <chrono>
 #include <cstdio>
 #include <vector>
@@ -27,7 +30,7 @@ int main(int argc, char **argv) {
   if (argc < 2) {
     std::fprintf(stderr,
                  "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm] "
-                 "[followed_cloud.ply] [stream] [world_mesh.ply]\n",
+                 "[followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply]\n",
                  argv[0]);
     return 2;
   }
@@ -198,6 +201,30 @@ int main(int argc, char **argv) {
       return 1;
     }
     std::printf("world: %lld bricks, %lld triangles\n", (long long)nb, (long long)nt);
+  }
+  if (argc > 10 && argv[10][0]) {  // the window's mesh with shared vertices and a face list
+    int64_t nv = 0, nt = 0;
+    if (kfx_extract_mesh_indexed(ctx, nullptr, 0, nullptr, 0, &nv, &nt) != KFX_OK ||
+        kfx_save_mesh_indexed(ctx, argv[10]) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    std::printf("indexed: %lld vertices, %lld triangles\n", (long long)nv, (long long)nt);
+  }
+  if (stream && argc > 11 && argv[11][0]) {  // and the world's
+    int64_t nb = 0, nv = 0, nt = 0;
+    if (kfx_world_bricks(ctx, store, nullptr, 0, &nb) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    bricks.resize((size_t)nb);
+    if ((nb > 0 && kfx_world_bricks(ctx, store, bricks.data(), nb, &nb) != KFX_OK) ||
+        kfx_world_mesh_indexed(ctx, bricks.data(), nb, nullptr, 0, nullptr, 0, &nv, &nt) != KFX_OK ||
+        kfx_save_world_mesh_indexed(ctx, store, argv[11]) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    std::printf("world indexed: %lld bricks, %lld vertices, %lld triangles\n", (long long)nb, (long long)nv, (long long)nt);
   }
   if (stream) {
     int64_t held = 0;

@@ -20,7 +20,7 @@ from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, Intr
 
 __all__ = ["KinectFusion", "KfxError", "Dataset", "png_info", "png_read_bgr8", "png_read_depth", "parse_intr",
            "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "write_ply_attr", "write_ply_mesh_attr",
-           "write_ppm", "shift_for_pose", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
+           "write_ply_mesh_indexed", "write_ppm", "shift_for_pose", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
            "default_params", "KFX_FRAME_CUR", "KFX_FRAME_PREV", "KFX_OK", "KFX_TRACKING_LOST", "EXPORTS"]
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,6 +46,8 @@ EXPORTS = [
     "kfx_brick_store_put", "kfx_brick_store_count", "kfx_brick_store_take_window",
     "kfx_world_points_attr", "kfx_world_mesh_attr", "kfx_get_world_ms", "kfx_brick_store_copy", "kfx_world_bricks",
     "kfx_save_world_mesh",
+    "kfx_extract_mesh_indexed", "kfx_world_mesh_indexed", "kfx_get_indexed_ms", "kfx_write_ply_mesh_indexed",
+    "kfx_save_mesh_indexed", "kfx_save_world_mesh_indexed",
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks", "kfx_debug_extract_units", "kfx_debug_scan",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
@@ -171,6 +173,12 @@ def lib():
         "kfx_brick_store_copy": ([vp, vp, C.c_int64, P(C.c_int64)], i),
         "kfx_world_bricks": ([vp, vp, vp, C.c_int64, P(C.c_int64)], i),
         "kfx_save_world_mesh": ([vp, vp, C.c_char_p, C.c_int64], i),
+        "kfx_extract_mesh_indexed": ([vp, vp, C.c_int64, vp, C.c_int64, P(C.c_int64), P(C.c_int64)], i),
+        "kfx_world_mesh_indexed": ([vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, P(C.c_int64), P(C.c_int64)], i),
+        "kfx_get_indexed_ms": ([vp, P(f)], i),
+        "kfx_write_ply_mesh_indexed": ([C.c_char_p, vp, C.c_int64, vp, C.c_int64], i),
+        "kfx_save_mesh_indexed": ([vp, C.c_char_p], i),
+        "kfx_save_world_mesh_indexed": ([vp, vp, C.c_char_p], i),
         "kfx_volume_checksum": ([vp, P(C.c_uint64)], i),
         "kfx_write_ply": ([C.c_char_p, P(f), C.c_int64], i),
         "kfx_save_pointcloud": ([vp, C.c_char_p, C.c_int64], i),
@@ -279,6 +287,15 @@ def write_ply_mesh_attr(path: str, tris: np.ndarray):
     t = np.ascontiguousarray(tris, np.dtype(VERTEX_DTYPE)).reshape(-1, 3)
     _check(lib().kfx_write_ply_mesh_attr(path.encode(), t.ctypes.data_as(C.c_void_p), t.shape[0]),
            "kfx_write_ply_mesh_attr")
+
+
+def write_ply_mesh_indexed(path: str, verts: np.ndarray, tris: np.ndarray):
+    """ASCII PLY of an indexed mesh: (V,) VERTEX_DTYPE vertices and (T, 3) uint32 faces."""
+    v = np.ascontiguousarray(verts, np.dtype(VERTEX_DTYPE)).ravel()
+    t = np.ascontiguousarray(tris, np.uint32).reshape(-1, 3)
+    _check(lib().kfx_write_ply_mesh_indexed(path.encode(), v.ctypes.data_as(C.c_void_p) if len(v) else None, len(v),
+                                            t.ctypes.data_as(C.c_void_p) if len(t) else None, len(t)),
+           "kfx_write_ply_mesh_indexed")
 
 
 def png_info(path: str) -> tuple:
@@ -900,6 +917,56 @@ class KinectFusion:
         a = (C.c_float * 3)()
         _check(lib().kfx_get_world_ms(self._h, a), "kfx_get_world_ms")
         return {"table": a[0], "count": a[1], "emit": a[2]}
+
+    # ---- indexed mesh ----------------------------------------
+    def _indexed(self, call, fill: bool):
+        """call(verts, cap_verts, tris, cap_tris, n_verts, n_tris): size, then (fill) fill."""
+        nv, nt = C.c_int64(), C.c_int64()
+        call(None, 0, None, 0, C.byref(nv), C.byref(nt))
+        if not fill:
+            return int(nv.value), int(nt.value)
+        verts, tris = np.empty(int(nv.value), np.dtype(VERTEX_DTYPE)), np.empty((int(nt.value), 3), np.uint32)
+        if len(verts):
+            call(verts.ctypes.data_as(C.c_void_p), len(verts), tris.ctypes.data_as(C.c_void_p) if len(tris) else None,
+                 len(tris), C.byref(nv), C.byref(nt))
+            assert (nv.value, nt.value) == (len(verts), len(tris))
+        return verts, tris
+
+    def _window_indexed(self, *a):
+        _check(lib().kfx_extract_mesh_indexed(self._h, *a), "kfx_extract_mesh_indexed")
+
+    def extract_mesh_indexed(self):
+        """kfx_extract_mesh_indexed: (verts (V,) VERTEX_DTYPE, tris (T, 3) uint32); verts[tris] is
+        extract_mesh_attr()'s soup, each vertex (grid edge) stored once."""
+        return self._indexed(self._window_indexed, True)
+
+    def indexed_count(self) -> tuple:
+        """(vertices, triangles) of extract_mesh_indexed, count and scans only."""
+        return self._indexed(self._window_indexed, False)
+
+    def world_mesh_indexed(self, bricks):
+        """kfx_world_mesh_indexed: extract_mesh_indexed of the world `bricks` ((N,) BRICK_DTYPE)."""
+        a = _bricks(bricks)
+
+        def call(*rest):
+            _check(lib().kfx_world_mesh_indexed(self._h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a), *rest),
+                   "kfx_world_mesh_indexed")
+        return self._indexed(call, True)
+
+    def indexed_ms(self) -> dict:
+        """Device ms of the last extract_mesh_indexed / world_mesh_indexed / indexed_count: the
+        world's neighbour table (0 in the window form), counts + scans, vertex emit, index emit."""
+        a = (C.c_float * 4)()
+        _check(lib().kfx_get_indexed_ms(self._h, a), "kfx_get_indexed_ms")
+        return {"table": a[0], "count": a[1], "verts": a[2], "tris": a[3]}
+
+    def save_mesh_indexed(self, path: str):
+        _check(lib().kfx_save_mesh_indexed(self._h, path.encode()), "kfx_save_mesh_indexed")
+
+    def save_world_mesh_indexed(self, path: str, store: "BrickStore | None" = None):
+        """kfx_save_world_mesh_indexed: the world's indexed mesh (window and store) as an ASCII PLY."""
+        _check(lib().kfx_save_world_mesh_indexed(self._h, store._h if store is not None else None, path.encode()),
+               "kfx_save_world_mesh_indexed")
 
     def extract_mesh(self, cap: int = 50_000_000) -> np.ndarray:
         """Marching-cubes triangles, (N, 3, 3) float32 world coordinates (canonical order)."""
