@@ -723,6 +723,63 @@ int kfx_write_ply_mesh_indexed(const char *path, const kfx_vertex *verts, int64_
 int kfx_save_mesh_indexed(kfx_ctx *ctx, const char *path);
 int kfx_save_world_mesh_indexed(kfx_ctx *ctx, const kfx_brick_store *store, const char *path);
 
+/* ---- world view: free-viewpoint render of window plus evicted bricks
+ * Added under ABI version 2, nothing else changed.  kfx_render_view sees the
+ * window only; these render a world (a brick list as in the world map above:
+ * strictly ascending, an absent brick unobserved) from any camera.
+ *
+ * A box is origin[3] (world voxels, each a multiple of 8) and dims[3] (voxels,
+ * each >= 1, not necessarily a multiple of 8; voxels of a brick past the box
+ * and bricks wholly outside it are ignored).  The default box (both pointers
+ * NULL) is the list's bounding box in bricks padded by one brick on every side:
+ * origin_k = 8 (min b_k - 1), dims_k = 8 (max b_k - min b_k + 3).  The raycast
+ * never reads a volume's outermost voxel layer; the pad keeps every listed
+ * voxel clear of it.
+ *
+ * The world view is by definition kfx_render_view (maps and all three images)
+ * of a virtual dense volume: dims = the box's; voxel size vs_k = volu_range[k] /
+ * (float)volu_dims[k] of the context; range_k = volu_range[k] where dims_k ==
+ * volu_dims[k], else (float)dims_k * vs_k; voxel (x, y, z) holds world voxel
+ * origin + (x, y, z) of the list; pose R0, t = t0 + R0 (origin * vs) computed as
+ * kfx_shift_volume computes its pose (float32, no contraction, that operation
+ * order); cam2vol = pose^-1 * cam_pose; KFX_VIEW_COLOR with "lies in the
+ * volume" read as "lies in the box".  With the box set to the window
+ * (kfx_get_volume_origin, volu_dims) and the window's bricks it equals
+ * kfx_render_view byte for byte.  A ray's samples start where it enters the
+ * box, so the box is part of the result: two boxes around the same bricks give
+ * slightly different images.
+ *
+ * kfx_world_view_load: uploads the records and builds what the march needs (a
+ * grid over the box's bricks and the raycast's skip maps) in buffers of its
+ * own: the kfx_world_* extraction calls and this one do not disturb each other.
+ * The buffers grow on demand and are freed in kfx_destroy.  The loaded world
+ * replaces the previous one; n = 0 unloads it.  It is a snapshot of the list:
+ * kfx_reset, frames, shifts and restores do not touch it, and the list may be
+ * freed once the call returns.  Stream ordering and blocking as
+ * kfx_world_mesh_attr.  KFX_ERR_ARG, the previous world kept: that call's list
+ * checks; exactly one of origin / dims NULL; an origin component that is no
+ * multiple of 8 or with |origin_k| >= 2^23; a dims component below 1 or above
+ * 2^15; a box of more than 2^26 bricks (a default box too).  KFX_ERR_STATE: a
+ * slab of a world larger than 1.  KFX_ERR_OOM when a device buffer cannot be
+ * allocated (no world is loaded then).
+ *
+ * kfx_world_view: kfx_render_view's arguments, checks, stream behaviour and
+ * blocking; it reads the loaded world only, writes nothing the tracker reads,
+ * keeps captured graphs and leaves a pending tracking status to the next
+ * kfx_synchronize.  KFX_ERR_STATE when no world is loaded.
+ *
+ * kfx_get_world_view_ms: device ms (HIP events) of [0] the last load's device
+ * work without the upload, [1] the last render's launch.
+ * kfx_save_world_view: kfx_world_bricks, kfx_world_view_load with the default
+ * box, kfx_world_view, kfx_write_ppm (an empty world: a black image). */
+int kfx_world_view_load(kfx_ctx *ctx, const kfx_brick *bricks, int64_t n,
+                        const int origin[3], const int dims[3]);
+int kfx_world_view(kfx_ctx *ctx, const kfx_intrinsics *view, const kfx_pose *cam_pose,
+                   int type, uint8_t *out, float *vmap, float *nmap, float *ts);
+int kfx_get_world_view_ms(kfx_ctx *ctx, float out_ms[2]);
+int kfx_save_world_view(kfx_ctx *ctx, const kfx_brick_store *store, const kfx_intrinsics *view,
+                        const kfx_pose *cam_pose, int type, const char *path);
+
 /* ---- dataset front-end (host only; no GPU needed) --------------------------
  * depth_sensor in its DATASET build (depth_sensor.cpp:11-46 open, :186-196
  * getFrame) without OpenCV: the PNG files of `<dir>/color` and `<dir>/depth` in

@@ -176,6 +176,15 @@ class kinectfusion {
   void saveColoredMesh(std::string path) {
     if (kfx_save_mesh_attr(ctx_, path.c_str(), 0) != KFX_OK) throw std::runtime_error(kfx_last_error());
   }
+  // The volume (merged with `store`, which may be null: the bricks a moving
+  // volume streamed out) in fused colour from `pose` through the sensor's
+  // intrinsics, as a binary PPM (kfx_save_world_view).
+  void saveWorldView(std::string path, const cv::Affine3f &pose, const kfx_brick_store *store = nullptr) {
+    const kfx_intrinsics ci{intr_.width, intr_.height, intr_.fx, intr_.fy, intr_.cx, intr_.cy};
+    const kfx_pose p = to_kfx(pose);
+    if (kfx_save_world_view(ctx_, store, &ci, &p, KFX_VIEW_COLOR, path.c_str()) != KFX_OK)
+      throw std::runtime_error(kfx_last_error());
+  }
   cv::Affine3f getCurCameraPose() { return pose_record.back(); }
   void release() {
     if (ctx_) kfx_destroy(ctx_);

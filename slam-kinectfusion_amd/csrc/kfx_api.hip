@@ -1148,6 +1148,10 @@ int kfx_destroy(kfx_ctx *c) {
   for (hipEvent_t e : c->ev_world)
     if (e) (void)hipEventDestroy(e);
   if (c->world_tris) (void)hipFree(c->world_tris);
+  for (void *b : c->wv_buf)
+    if (b) (void)hipFree(b);
+  for (hipEvent_t e : c->ev_wv)
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_indexed)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : c->ev)

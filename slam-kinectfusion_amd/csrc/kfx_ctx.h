@@ -184,6 +184,20 @@ struct kfx_ctx {
   size_t world_tris_cap = 0;
   hipEvent_t ev_indexed[6]{};
   float indexed_ms[4]{};
+  // world view: the loaded world.  Buffers of its own (grown
+  // on demand, kept, freed in kfx_destroy): [0] the records, [1] the grid over
+  // the box's bricks, [2] / [3] the box's occupancy maps.  wv_vol describes the
+  // box as a volume (kfx_internal.h WorldGrid); wv_n = 0: nothing loaded.  The
+  // images go through kfx_render_view's staging buffers.  Events: the last
+  // load's device work [0, 1], the last render's launch [2, 3].
+  void *wv_buf[4]{};
+  size_t wv_cap[4]{};
+  VolView wv_vol{};
+  size_t wv_n = 0, wv_cells = 0;
+  int wv_origin[3] = {0, 0, 0};
+  DevPose wv_pose{};
+  hipEvent_t ev_wv[4]{};
+  float wv_ms[2]{};
   uint8_t *mc_tab = nullptr;     // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded

@@ -1,8 +1,8 @@
 // kfx_export.hip — the host side of what reads the model out: the
 // free-viewpoint render, point cloud / mesh extraction and PLY files, the
-// moving volume, bricks out and back in, the world map and the indexed mesh
-// (DESIGN.md §18, §20-§24).  Host code only (no __global__ function: the kernels are in
-// kfx_extract / kfx_view / kfx_shift / kfx_world.hip); no frame runs any of it.
+// moving volume, bricks out and back in, the world map, the indexed mesh and the world view
+// (DESIGN.md §18, §20-§25).  Host code only (no __global__ function: the kernels are in
+// kfx_extract / kfx_view / kfx_shift / kfx_world / kfx_world_view.hip); no frame runs any of it.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -300,10 +300,8 @@ static DevPose host_pose_inv(const DevPose &a) {
   return r;
 }
 
-int kfx_render_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_pose, int type, uint8_t *out,
-                    float *vmap, float *nmap, float *ts) {
-  int r = check_ctx(c);
-  if (r) return r;
+// the argument checks kfx_render_view and kfx_world_view share
+static int view_args(const kfx_intrinsics *view, const kfx_pose *cam_pose, const uint8_t *out, int type) {
   if (!view || !cam_pose || !out) return set_err(KFX_ERR_ARG, "null argument");
   if (type < KFX_VIEW_PHONG || type > KFX_VIEW_COLOR) return set_err(KFX_ERR_ARG, "view type outside 0..2");
   if (view->width < 1 || view->height < 1 || (int64_t)view->width * view->height > ((int64_t)1 << 26))
@@ -313,6 +311,14 @@ int kfx_render_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_
     return set_err(KFX_ERR_ARG, "view intrinsics: finite, fx and fy non-zero");
   for (int i = 0; i < 12; ++i)
     if (!std::isfinite(i < 9 ? cam_pose->R[i] : cam_pose->t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite view pose");
+  return KFX_OK;
+}
+
+int kfx_render_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_pose, int type, uint8_t *out,
+                    float *vmap, float *nmap, float *ts) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = view_args(view, cam_pose, out, type))) return r;
   if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "render_view on one slab of several");
   const size_t np = (size_t)view->width * view->height;
   const bool maps = vmap || nmap || ts;
@@ -1070,6 +1076,161 @@ int kfx_save_world_mesh_indexed(kfx_ctx *c, const kfx_brick_store *store, const 
                       [&](kfx_vertex *v, int64_t cv, uint32_t *t, int64_t ct, int64_t *nv, int64_t *nt) {
                         return kfx_world_mesh_indexed(c, bricks.data(), nb, v, cv, t, ct, nv, nt);
                       });
+}
+
+// ---- world view ----------------------------------------------------
+
+int kfx_world_view_load(kfx_ctx *c, const kfx_brick *bricks, int64_t n, const int origin[3], const int dims[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = world_args(c, bricks, n, nullptr, 0))) return r;
+  if ((origin == nullptr) != (dims == nullptr)) return set_err(KFX_ERR_ARG, "world_view_load: origin and dims go together");
+  if (n > ((int64_t)1 << 28)) return set_err(KFX_ERR_OOM, "world: more bricks than the record buffer can hold");
+  if (n == 0) {  // unload (the buffers stay for the next world)
+    c->wv_n = 0;
+    c->wv_ms[0] = 0.f;
+    return KFX_OK;
+  }
+  int64_t o[3], d[3];
+  if (origin) {
+    for (int k = 0; k < 3; ++k) o[k] = origin[k], d[k] = dims[k];
+  } else {  // the list's bounding box in bricks, one brick of padding on every side
+    int64_t lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) lo[k] = hi[k] = bricks[0].b[k];
+    for (int64_t i = 1; i < n; ++i)
+      for (int k = 0; k < 3; ++k) {
+        lo[k] = std::min<int64_t>(lo[k], bricks[i].b[k]);
+        hi[k] = std::max<int64_t>(hi[k], bricks[i].b[k]);
+      }
+    for (int k = 0; k < 3; ++k) o[k] = 8 * (lo[k] - 1), d[k] = 8 * (hi[k] - lo[k] + 3);
+  }
+  int64_t nb[3];
+  for (int k = 0; k < 3; ++k) {
+    if (o[k] % 8) return set_err(KFX_ERR_ARG, "world_view_load: origin components must be multiples of 8 voxels");
+    if (o[k] <= -((int64_t)1 << 23) || o[k] >= ((int64_t)1 << 23))
+      return set_err(KFX_ERR_ARG, "world_view_load: an origin component outside (-2^23, 2^23)");
+    if (d[k] < 1 || d[k] > (1 << 15)) return set_err(KFX_ERR_ARG, "world_view_load: a dims component outside 1..2^15");
+    nb[k] = (d[k] + 7) / 8;
+  }
+  if (nb[0] * nb[1] * nb[2] > ((int64_t)1 << 26)) return set_err(KFX_ERR_ARG, "world_view_load: a box of more than 2^26 bricks");
+  // the box as a volume: make_vol's map extents for a whole volume of these dims
+  VolView v{};
+  v.X = (int)d[0], v.Y = (int)d[1], v.Z = (int)d[2];
+  v.zb = 0, v.zn = v.Z, v.own0 = 0, v.own1 = v.Z;
+  v.tiles_x = (int)nb[0], v.tiles_y = (int)nb[1];
+  v.slice = (size_t)v.X * v.Y;
+  v.bz0 = 0, v.nbz = (int)nb[2], v.bw = (v.nbz + 63) / 64;
+  v.sz0 = 0, v.nsz = ((v.Z - 1) >> 5) + 1, v.sw = (v.nsz + 31) / 32;
+  v.stx = (v.tiles_x + 3) / 4, v.sty = (v.tiles_y + 3) / 4;
+  for (int k = 0; k < 3; ++k) {
+    v.vs[k] = c->vol.vs[k];
+    v.range[k] = d[k] == c->p.volu_dims[k] ? c->p.volu_range[k] : (float)d[k] * v.vs[k];
+  }
+  v.trunc = c->vol.trunc, v.inv_trunc = c->vol.inv_trunc;
+  const size_t nn = (size_t)n, cells = (size_t)(nb[0] * nb[1] * nb[2]);
+  if ((r = make_events(c->ev_wv, 4))) return r;
+  // from here on the previous world is gone (its buffers are reused)
+  c->wv_n = 0;
+  void **buf = c->wv_buf;
+  size_t *bcap = c->wv_cap;
+  if ((r = reserve(&buf[0], &bcap[0], nn * sizeof(kfx_brick), "world_view_load")) ||
+      (r = reserve(&buf[1], &bcap[1], cells * 4, "world_view_load")) ||
+      (r = reserve(&buf[2], &bcap[2], v.bocc_bytes(), "world_view_load")) ||
+      (r = reserve(&buf[3], &bcap[3], v.socc_bytes(), "world_view_load")))
+    return r;
+  v.bocc = (unsigned long long *)buf[2];
+  v.socc = (uint32_t *)buf[3];
+  const WorldGrid wg = {buf[0], (uint32_t *)buf[1], nn, cells};
+  const int oi[3] = {(int)o[0], (int)o[1], (int)o[2]};
+  hipStream_t s = c->stream;  // behind every queued frame, as kfx_world_mesh_attr
+  HIPCHK(hipMemcpyAsync(buf[0], bricks, nn * sizeof(kfx_brick), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(c->ev_wv[0], s));
+  launch_world_view_load(s, v, wg, oi);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_wv[1], s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipEventElapsedTime(&c->wv_ms[0], c->ev_wv[0], c->ev_wv[1]));
+  // the box's pose: kfx_shift_volume's formula at this origin (set_volume_origin)
+  const kfx_pose &p0 = c->volu_pose0;
+  float dd[3];
+  for (int k = 0; k < 3; ++k) dd[k] = (float)oi[k] * v.vs[k];
+  c->wv_pose = to_dev(p0);
+  for (int i = 0; i < 3; ++i) {
+    const float a = p0.R[3 * i] * dd[0], b = p0.R[3 * i + 1] * dd[1], e = p0.R[3 * i + 2] * dd[2];
+    const float sum = (a + b) + e;
+    c->wv_pose.t[i] = p0.t[i] + sum;
+  }
+  c->wv_vol = v;
+  c->wv_cells = cells;
+  for (int k = 0; k < 3; ++k) c->wv_origin[k] = oi[k];
+  c->wv_n = nn;
+  return KFX_OK;
+}
+
+int kfx_world_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_pose, int type, uint8_t *out, float *vmap,
+                   float *nmap, float *ts) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = view_args(view, cam_pose, out, type))) return r;
+  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "world_view on one slab of several");
+  if (c->wv_n == 0) return set_err(KFX_ERR_STATE, "world_view: no world is loaded (kfx_world_view_load)");
+  const size_t np = (size_t)view->width * view->height;
+  const bool maps = vmap || nmap || ts;
+  if ((r = reserve((void **)&c->view_out, &c->view_out_cap, 3 * np, "world_view"))) return r;
+  if (maps && (r = reserve((void **)&c->view_maps, &c->view_maps_cap, 28 * np, "world_view"))) return r;
+  if ((r = make_events(c->ev_wv, 4))) return r;
+  float *dv = vmap ? c->view_maps : nullptr, *dn = nmap ? c->view_maps + 3 * np : nullptr,
+        *dt = ts ? c->view_maps + 6 * np : nullptr;
+  const DevPose cam = to_dev(*cam_pose);
+  const DevPose c2v = host_pose_mul(host_pose_inv(c->wv_pose), cam);
+  const LevelGeom g = {view->width, view->height, view->fx, view->fy, view->cx, view->cy};
+  VolView v = c->wv_vol;
+  v.force64 = c->vol.force64;
+  const WorldGrid wg = {c->wv_buf[0], (uint32_t *)c->wv_buf[1], c->wv_n, c->wv_cells};
+  // on the frame stream; it reads the loaded world only and writes the view's buffers
+  HIPCHK(hipEventRecord(c->ev_wv[2], c->stream));
+  launch_world_view(c->stream, v, wg, g, c2v, cam.t, type, c->view_out, dv, dn, dt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_wv[3], c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->view_out, 3 * np, hipMemcpyDeviceToHost, c->stream));
+  if (vmap) HIPCHK(hipMemcpyAsync(vmap, dv, 12 * np, hipMemcpyDeviceToHost, c->stream));
+  if (nmap) HIPCHK(hipMemcpyAsync(nmap, dn, 12 * np, hipMemcpyDeviceToHost, c->stream));
+  if (ts) HIPCHK(hipMemcpyAsync(ts, dt, 4 * np, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->wv_ms[1], c->ev_wv[2], c->ev_wv[3]));
+  return KFX_OK;
+}
+
+int kfx_get_world_view_ms(kfx_ctx *c, float out_ms[2]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  out_ms[0] = c->wv_ms[0];
+  out_ms[1] = c->wv_ms[1];
+  return KFX_OK;
+}
+
+int kfx_save_world_view(kfx_ctx *c, const kfx_brick_store *store, const kfx_intrinsics *view, const kfx_pose *cam_pose,
+                        int type, const char *path) {
+  if (!path) return set_err(KFX_ERR_ARG, "null path");
+  if (!view || view->width < 1 || view->height < 1 || (int64_t)view->width * view->height > ((int64_t)1 << 26))
+    return set_err(KFX_ERR_ARG, "view size: width, height >= 1 and width * height <= 2^26");
+  int64_t nb = 0;
+  int r = kfx_world_bricks(c, store, nullptr, 0, &nb);
+  if (r) return r;
+  std::vector<kfx_brick> bricks;
+  std::vector<uint8_t> img;
+  try {
+    bricks.resize((size_t)nb);
+    img.assign(3 * (size_t)view->width * view->height, 0);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "save_world_view: out of memory");
+  }
+  if (nb > 0 && (r = kfx_world_bricks(c, store, bricks.data(), nb, &nb))) return r;
+  if ((r = kfx_world_view_load(c, bricks.data(), nb, nullptr, nullptr))) return r;
+  // an empty world is an empty image (nothing is loaded then)
+  if (nb > 0 && (r = kfx_world_view(c, view, cam_pose, type, img.data(), nullptr, nullptr, nullptr))) return r;
+  return kfx_write_ppm(path, img.data(), view->width, view->height);
 }
 
 int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *vp, const kfx_pose *cam, float ahead_m, int shift[3]) {

@@ -1,5 +1,5 @@
 // kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip,
-// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip) and the host runtime (kfx_api.hip, kfx_export.hip).  Not part of the public ABI.
+// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip, kfx_world_view.hip) and the host runtime (kfx_api.hip, kfx_export.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -460,6 +460,25 @@ void launch_world_indexed(hipStream_t s, const void *recs, size_t n, const int32
                           const float vs[3], const uint8_t *tab, int pass, unsigned *vcounts, unsigned *tcounts,
                           const unsigned long long *voff, const unsigned long long *toff, void *verts, uint16_t *keys,
                           uint32_t *tris);
+
+// ---- kfx_world_view.hip -----------------------------------------------------
+// free-viewpoint render of a world.  The loaded world: n
+// kfx_brick records in device memory and a dense grid over the box's bricks,
+//   grid[(by * tiles_x + bx) * nbz + bz] = record number + 1, 0: no brick
+// beside a VolView-shaped descriptor of the box: X, Y, Z = its dims, tiles_x /
+// tiles_y / nbz = its bricks per axis, zb = 0, zn = Z, vs, range, the
+// occupancy maps (bocc / socc and their extents) and force64; no voxel arrays.
+struct WorldGrid {
+  const void *recs;
+  uint32_t *grid;
+  size_t n, cells;
+};
+// grid and occupancy maps of the records whose brick lies in the box at voxel
+// origin `origin` (multiples of 8); every other record is ignored
+void launch_world_view_load(hipStream_t s, VolView v, WorldGrid wg, const int origin[3]);
+// launch_view on the loaded world
+void launch_world_view(hipStream_t s, VolView v, WorldGrid wg, LevelGeom g, DevPose cam2vol, const float eye[3], int type,
+                       uint8_t *out, float *vmap, float *nmap, float *ts);
 
 // ---- kfx_volume_io.hip ----------------------------------------------------
 void launch_export_records(hipStream_t s, VolView v, int z0, int nz, uint64_t *dst);

@@ -17,9 +17,13 @@
 // surface once wherever the window stands; a tenth argument writes the window's
 // indexed mesh, DESIGN.md §24: shared vertices and a face list,
 // kfx_save_mesh_indexed; an eleventh, with the eighth, the world's,
-// kfx_save_world_mesh_indexed).
+// kfx_save_world_mesh_indexed; a twelfth, with the eighth, world_view.ppm, DESIGN.md
+// §25: window plus store in fused colour, seen from the first recorded pose
+// through the dataset's intrinsics, kfx_save_world_view: the whole map, also
+// where the window has moved on).
 //   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
 //                  [followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply]
+//                  [world_view.ppm]
 #include <chrono>
 #include <cstdio>
 #include <vector>
@@ -30,7 +34,8 @@ int main(int argc, char **argv) {
   if (argc < 2) {
     std::fprintf(stderr,
                  "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm] "
-                 "[followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply]\n",
+                 "[followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply] "
+                 "[world_view.ppm]\n",
                  argv[0]);
     return 2;
   }
@@ -225,6 +230,18 @@ int main(int argc, char **argv) {
       return 1;
     }
     std::printf("world indexed: %lld bricks, %lld vertices, %lld triangles\n", (long long)nb, (long long)nv, (long long)nt);
+  }
+  if (stream && argc > 12 && argv[12][0]) {  // the whole map from where the run began
+    kfx_pose first;
+    int got = 0;
+    if (kfx_get_pose_record(ctx, &first, 1, &got) != KFX_OK || got < 1 ||
+        kfx_save_world_view(ctx, store, &intr, &first, KFX_VIEW_COLOR, argv[12]) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+    float ms[2] = {0.f, 0.f};
+    kfx_get_world_view_ms(ctx, ms);
+    std::printf("world view: load %.3f ms, render %.3f ms\n", ms[0], ms[1]);
   }
   if (stream) {
     int64_t held = 0;

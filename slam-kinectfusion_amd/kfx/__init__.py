@@ -48,6 +48,7 @@ EXPORTS = [
     "kfx_save_world_mesh",
     "kfx_extract_mesh_indexed", "kfx_world_mesh_indexed", "kfx_get_indexed_ms", "kfx_write_ply_mesh_indexed",
     "kfx_save_mesh_indexed", "kfx_save_world_mesh_indexed",
+    "kfx_world_view_load", "kfx_world_view", "kfx_get_world_view_ms", "kfx_save_world_view",
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks", "kfx_debug_extract_units", "kfx_debug_scan",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
@@ -179,6 +180,10 @@ def lib():
         "kfx_write_ply_mesh_indexed": ([C.c_char_p, vp, C.c_int64, vp, C.c_int64], i),
         "kfx_save_mesh_indexed": ([vp, C.c_char_p], i),
         "kfx_save_world_mesh_indexed": ([vp, vp, C.c_char_p], i),
+        "kfx_world_view_load": ([vp, vp, C.c_int64, P(i), P(i)], i),
+        "kfx_world_view": ([vp, P(Intrinsics), P(Pose), i, P(C.c_uint8), P(f), P(f), P(f)], i),
+        "kfx_get_world_view_ms": ([vp, P(f)], i),
+        "kfx_save_world_view": ([vp, vp, P(Intrinsics), P(Pose), i, C.c_char_p], i),
         "kfx_volume_checksum": ([vp, P(C.c_uint64)], i),
         "kfx_write_ply": ([C.c_char_p, P(f), C.c_int64], i),
         "kfx_save_pointcloud": ([vp, C.c_char_p, C.c_int64], i),
@@ -917,6 +922,45 @@ class KinectFusion:
         a = (C.c_float * 3)()
         _check(lib().kfx_get_world_ms(self._h, a), "kfx_get_world_ms")
         return {"table": a[0], "count": a[1], "emit": a[2]}
+
+    # ---- world view -------------------------------------------
+    def world_view_load(self, bricks, box=None):
+        """kfx_world_view_load: make the (N,) BRICK_DTYPE world `bricks` the one world_view renders
+        (a snapshot; an empty list unloads).  box = (origin, dims) in world voxels, None: the list's
+        bounding box padded by one brick on every side."""
+        a = _bricks(bricks)
+        o = d = None
+        if box is not None:
+            o, d = (None if q is None else (C.c_int * 3)(*[int(x) for x in q]) for q in box)
+        _check(lib().kfx_world_view_load(self._h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a), o, d),
+               "kfx_world_view_load")
+
+    def world_view(self, intr, pose, kind: str = "phong", maps: bool = False):
+        """kfx_world_view: render_view of the loaded world (same arguments, same return shapes)."""
+        I = Intrinsics.from_any(intr)
+        P = pose if isinstance(pose, Pose) else Pose.from_matrix(pose)
+        h, w = max(I.height, 0), max(I.width, 0)
+        out = np.zeros((h, w, 3), np.uint8)
+        vm = np.zeros((h, w, 3), np.float32) if maps else None
+        nm = np.zeros((h, w, 3), np.float32) if maps else None
+        ts = np.zeros((h, w), np.float32) if maps else None
+        _check(lib().kfx_world_view(self._h, C.byref(I), C.byref(P), VIEW_KINDS[kind],
+                                    out.ctypes.data_as(C.POINTER(C.c_uint8)), fptr(vm) if maps else None,
+                                    fptr(nm) if maps else None, fptr(ts) if maps else None), "kfx_world_view")
+        return (out, vm, nm, ts) if maps else out
+
+    def world_view_ms(self) -> dict:
+        """Device ms of the last world_view_load (without the upload) and the last world_view (HIP events)."""
+        a = (C.c_float * 2)()
+        _check(lib().kfx_get_world_view_ms(self._h, a), "kfx_get_world_view_ms")
+        return {"load": a[0], "render": a[1]}
+
+    def save_world_view(self, path: str, intr, pose, kind: str = "color", store: "BrickStore | None" = None):
+        """kfx_save_world_view: window plus store seen from `pose` through `intr`, as a binary PPM."""
+        I = Intrinsics.from_any(intr)
+        P = pose if isinstance(pose, Pose) else Pose.from_matrix(pose)
+        _check(lib().kfx_save_world_view(self._h, store._h if store is not None else None, C.byref(I), C.byref(P),
+                                         VIEW_KINDS[kind], path.encode()), "kfx_save_world_view")
 
     # ---- indexed mesh (DESIGN.md §24) ----------------------------------------
     def _indexed(self, call, fill: bool):
