@@ -311,7 +311,9 @@ int kfx_stage_icp(kfx_ctx *ctx, kfx_pose *cam_pose_out);
 int kfx_stage_integrate(kfx_ctx *ctx, const kfx_pose *vol2cam,
                         int64_t *n_updated, int64_t *n_colored);
 /* device::raycast (tsdf_volume.cu:264-273) into PREV level 0, with cam2vol and
- * Rinv (row-major 3x3), then resizePointsNormals for levels >= 1. */
+ * Rinv (row-major 3x3), then resizePointsNormals for levels >= 1.  A slab
+ * context of world 1 runs the slab kernel and expands its payload into the
+ * same maps; one slab of several is refused (KFX_ERR_STATE). */
 int kfx_stage_raycast(kfx_ctx *ctx, const kfx_pose *cam2vol, const float Rinv[9]);
 
 /* ---- timing -------------------------------------------------------------- */

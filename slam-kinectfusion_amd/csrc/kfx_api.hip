@@ -2116,7 +2116,21 @@ int kfx_stage_raycast(kfx_ctx *c, const kfx_pose *cam2vol, const float Rinv[9]) 
   HIPCHK(hipMemcpyAsync(c->xpose, xp, sizeof(xp), hipMemcpyHostToDevice, c->stream));
   launch_raycast(c->stream, c->vol, c->L, c->g, c->cur, c->prev, c->st, c->pose_log,
                  to_dev(c->p.volu_pose), c->xpose, c->slab ? c->key_local : nullptr);
-  if (c->slab) launch_resize(c->stream, c->L, c->g, c->cur, c->prev, c->st, c->xpose);
+  if (c->slab) {
+    // The slab kernel leaves keys and the payload {Ts, normal}, not maps.  With
+    // the whole volume owned (world 1) the payload is the result: expand it at
+    // the explicit ray frame (the external combine's host code, kfx_slab_expand)
+    // into PREV level 0, then the levels above.
+    const size_t np = (size_t)c->intr.width * c->intr.height;
+    std::vector<uint32_t> pay(4 * np);
+    std::vector<float> maps(6 * np);
+    HIPCHK(hipMemcpyAsync(pay.data(), c->key_local + 2 * np, 16 * np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((r = kfx_slab_expand(pay.data(), &c->intr, cam2vol, Rinv, maps.data(), maps.data() + 3 * np))) return r;
+    HIPCHK(hipMemcpy(c->prev.v[0], maps.data(), 12 * np, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->prev.n[0], maps.data() + 3 * np, 12 * np, hipMemcpyHostToDevice));
+    launch_resize(c->stream, c->L, c->g, c->cur, c->prev, c->st, c->xpose);
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   return KFX_OK;

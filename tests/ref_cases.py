@@ -10,7 +10,7 @@ test_ref_parity.py runs every case on both and compares element by element, and
 compares both with the digests tools/ref_digests.py recorded from the
 reference (tests/golden/ref_digests.json); test_gpu_ref_digests.py holds
 libkfx to the same recorded digests.  Inputs come from the project's existing
-case tables (integrate_cases, icp_cases, view_cases, and the tables of
+case tables (integrate_cases, icp_cases, view_cases, ray_cases, and the tables of
 test_gpu_ray_chain / test_gpu_param_space / test_icp_restatement), imported as
 they stand.
 
@@ -29,6 +29,7 @@ import numpy as np
 import icp_cases as K
 import integrate_cases as IC
 import oracle as O
+import ray_cases as RS
 import test_gpu_param_space as PS
 import test_gpu_ray_chain as RC
 import test_icp_restatement as IR
@@ -424,6 +425,15 @@ def _view_case(dims, vname):
 VIEW_NAMES = ("off", "odd", "qvga", "own", "big", "miss")
 
 
+def _rayspace_case(name):
+    """A crafted case of ray_cases.py: its analytic volume raycast from its own ray frame."""
+    def run(B):
+        case = RS.CASES[name]
+        vol = B.new_volume(case.dims, case.range, RS.volume(case.vol))
+        return named(chain(B, *B.raycast(vol, case.intr, case.cam2vol, case.Rinv)))
+    return run
+
+
 # --------------------------------------------------------------------------
 # image kernels
 
@@ -669,6 +679,8 @@ for _d in VC.DIMS:
     for _n in VIEW_NAMES:
         CASES[f"view/{_d}/{_n}"] = _view_case(_d, _n)
         CASES[f"render/view/{_d}/{_n}"] = _render_case(f"view/{_d}/{_n}")
+for _n in RS.CASES:
+    CASES[f"rayspace/{_n}"] = _rayspace_case(_n)
 CASES["render/kat"] = _render_case("kat/")
 for _n in IMAGE:
     CASES[f"img/{_n}"] = _image_case(_n)
