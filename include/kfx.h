@@ -223,6 +223,17 @@ int kfx_debug_int_tiles(kfx_ctx *ctx, int on);
 #define KFX_ICP_PLAN_WORDS 16
 int kfx_debug_get_icp_sums(kfx_ctx *ctx, int64_t out[27]);
 int kfx_debug_cap_icp_blocks(kfx_ctx *ctx, int cap, int32_t plan[KFX_ICP_PLAN_WORDS]);
+/* Debug hook of the ICP step (added under ABI version 2, nothing
+ * else changed): the six doubles (rotation vector, translation) of the last
+ * ICP iteration that solved on this context, whichever kernel ran it; waits
+ * for the stream, changes nothing.  Defined after a track that returned
+ * KFX_OK and ran at least one iteration.
+ * With it, off the frame path: kfx_stage_icp on a slab context of world 1 with
+ * kfx_set_icp_allreduce on and no communicator runs the sharded loop (the
+ * per-iteration sums of rank 0 of 1, then the stand-alone solve kernel, no
+ * collective), and kfx_debug_cap_icp_blocks reports 3 in plan[3] for such a
+ * context.  Every other context behaves as before. */
+int kfx_debug_get_icp_step(kfx_ctx *ctx, double x[6]);
 /* Debug hooks of the extraction (added under ABI version 2,
  * nothing else changed).  The extraction sweeps (count, emit and pool pass of
  * kfx_extract_points / kfx_extract_mesh and their _attr forms) give every wave

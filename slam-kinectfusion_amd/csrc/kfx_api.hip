@@ -1599,6 +1599,21 @@ int kfx_debug_get_icp_sums(kfx_ctx *c, int64_t out[27]) {
   return KFX_OK;
 }
 
+int kfx_debug_get_icp_step(kfx_ctx *c, double x[6]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!x) return set_err(KFX_ERR_ARG, "null argument");
+  DevState s;
+  if ((r = read_state(c, &s))) return r;  // (synchronises the stream)
+  for (int k = 0; k < 6; ++k) x[k] = s.x[k];
+  return KFX_OK;
+}
+
+// kfx_stage_icp's sharded route: a slab context of world 1 with the partial
+// all-reduce on and no communicator (the one rank's band is the whole image, so
+// the sums need no collective)
+static bool stage_icp_sharded(const kfx_ctx *c) { return c->slab && c->world == 1 && c->icp_sharded && !c->comm; }
+
 int kfx_debug_cap_icp_blocks(kfx_ctx *c, int cap, int32_t plan[KFX_ICP_PLAN_WORDS]) {
   int r = check_ctx(c);
   if (r) return r;
@@ -1614,7 +1629,7 @@ int kfx_debug_cap_icp_blocks(kfx_ctx *c, int cap, int32_t plan[KFX_ICP_PLAN_WORD
     plan[0] = c->icp_persistent ? pl.stride : 0;
     plan[1] = pl.nblocks;
     plan[2] = pl.levels;
-    plan[3] = !c->icp_persistent || !c->icp_persistent_enabled ? 0 : c->icp_coop ? 2 : 1;
+    plan[3] = stage_icp_sharded(c) ? 3 : !c->icp_persistent || !c->icp_persistent_enabled ? 0 : c->icp_coop ? 2 : 1;
     for (int l = 0; l < pl.levels; ++l) {
       plan[4 + 3 * l] = c->icp_persistent && pl.stride ? pl.span[l] : 0;
       plan[5 + 3 * l] = pl.groups[l];
@@ -1985,7 +2000,17 @@ int kfx_stage_icp(kfx_ctx *c, kfx_pose *out) {
   s.icp_fail = 0;
   s.icp_pose = identity_pose();
   HIPCHK(hipMemcpyAsync(c->st, &s, sizeof(s), hipMemcpyHostToDevice, c->stream));
-  if (!try_icp_persistent(c, c->stream, 0)) {
+  if (stage_icp_sharded(c)) {
+    // enqueue_icp_sharded's loop as rank 0 of 1, without the collective: the
+    // sums of k_icp_acc (update = 0) solved by k_icp_solve
+    for (int level = c->L - 1; level >= 0; --level)
+      for (int it = 0; it < c->p.icp_iter_count[level]; ++it) {
+        launch_icp(c->stream, c->g[level], c->cur.v[level], c->cur.n[level], c->prev.v[level],
+                   c->prev.n[level], c->p.icp_dist_threshold, c->angle_thr, c->st,
+                   c->icp_shards, c->icp_ticket, 0, 0, 0, 1);
+        launch_icp_solve(c->stream, c->st);
+      }
+  } else if (!try_icp_persistent(c, c->stream, 0)) {
     for (int level = c->L - 1; level >= 0; --level) {
       for (int it = 0; it < c->p.icp_iter_count[level]; ++it)
         launch_icp(c->stream, c->g[level], c->cur.v[level], c->cur.n[level], c->prev.v[level],
@@ -2010,6 +2035,7 @@ int kfx_stage_icp(kfx_ctx *c, kfx_pose *out) {
   if (out) *out = to_api(s.icp_pose);
   const int failed = s.icp_fail;
   std::memcpy(s0.sums, s.sums, sizeof(s0.sums));  // the test seam keeps the last iteration's sums (kfx_debug_get_icp_sums)
+  std::memcpy(s0.x, s.x, sizeof(s0.x));           // and the last solved increment (kfx_debug_get_icp_step)
   HIPCHK(hipMemcpyAsync(c->st, &s0, sizeof(s0), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return failed ? KFX_TRACKING_LOST : KFX_OK;

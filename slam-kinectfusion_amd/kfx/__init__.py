@@ -51,6 +51,7 @@ EXPORTS = [
     "kfx_world_view_load", "kfx_world_view", "kfx_get_world_view_ms", "kfx_save_world_view",
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks", "kfx_debug_extract_units", "kfx_debug_scan",
+    "kfx_debug_get_icp_step",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
 ]
@@ -105,6 +106,7 @@ def lib():
         "kfx_debug_icp_band_ms": ([vp, i, i, i, P(C.c_float)], i),
         "kfx_debug_get_icp_sums": ([vp, P(C.c_int64)], i),
         "kfx_debug_cap_icp_blocks": ([vp, i, P(C.c_int32)], i),
+        "kfx_debug_get_icp_step": ([vp, P(C.c_double)], i),
         "kfx_debug_extract_units": ([vp, i], i),
         "kfx_debug_scan": ([vp, P(C.c_uint32), C.c_int64, P(C.c_uint64), P(C.c_uint64)], i),
         "kfx_get_icp_trace": ([vp, P(C.c_uint64), i], i),
@@ -678,10 +680,16 @@ class KinectFusion:
         _check(lib().kfx_debug_get_icp_sums(self._h, i64ptr(s)), "kfx_debug_get_icp_sums")
         return s
 
+    def debug_get_icp_step(self) -> np.ndarray:
+        """The six doubles (rotation vector, translation) of the last ICP iteration that solved."""
+        x = (C.c_double * 6)()
+        _check(lib().kfx_debug_get_icp_step(self._h, x), "kfx_debug_get_icp_step")
+        return np.array(x[:], np.float64)
+
     def debug_cap_icp_blocks(self, cap: int = 0) -> dict:
         """Plan the persistent ICP as if at most `cap` blocks were co-resident
         (0: the device's own figure; < 0: change nothing); returns the plan in effect: usable,
-        stride, nblocks, launch (0 none, 1 plain, 2 cooperative) and per level
+        stride, nblocks, launch (0 none, 1 plain, 2 cooperative, 3 the sharded loop of stage_icp) and per level
         span / groups / ppl."""
         a = (C.c_int32 * 16)()
         r = lib().kfx_debug_cap_icp_blocks(self._h, int(cap), a)
