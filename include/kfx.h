@@ -904,6 +904,93 @@ int kfx_slab_frame_local(kfx_ctx *ctx, const uint8_t *bgr, const float *depth_mm
                          uint32_t *payload);
 int kfx_slab_frame_finish(kfx_ctx *ctx, const uint32_t *payload);
 
+/* ---- ICP residual map and tracking quality ----------------
+ * Added under ABI version 2, nothing else changed.  How well the CUR maps of a
+ * level fit model maps under a relative pose: rigid_icp.cu:46-113's
+ * correspondence gates with the outcome handed out per pixel instead of
+ * folded into the 27 sums.
+ *
+ * Label, one byte per pixel of the level (w * h of them):
+ * KFX_ICP_UNCOVERED outside the floor-covered region xe = (w/32)*32,
+ * ye = (h/32)*32 the ICP never looks at; inside it the first gate that rejects
+ * the pixel, in the kernel's order: NaN current normal (x component); vcur.z > 0
+ * and the rounded projection inside the image; |vcur - vpre|^2 <= dist2_max;
+ * |ncur x npre|^2 <= sine2_max (the thresholds in kfx_stage_icp_accumulate's
+ * one-compare form; a NaN fails its gate); else KFX_ICP_ACCEPT.
+ * Residual: r = dot(npre, vpre - vcur) of an accepted pixel, the row's seventh
+ * entry in float32; 0.0f everywhere else.
+ * Record: n[k] pixels of label k (they sum to w * h); sum_r2 the sum over
+ * accepted pixels of rint(RN(r * r) * 2^32), exact and order-independent like
+ * the 27 sums (|r| is a row entry: the bound checked at kfx_create covers it);
+ * max_abs_r the largest |r| accepted, 0 when there is none.
+ *
+ * kfx_quality_figures (host only, no context):
+ *   fitness = n[0] / (double)(n[0] + n[2] + n[3] + n[4])   (0 when that is 0)
+ *   rmse    = sqrt(((double)sum_r2 / 4294967296.0) / (double)n[0])   (0 when n[0] is 0)
+ * in double in this order; KFX_ERR_ARG on a null pointer or a negative count.
+ *
+ * kfx_stage_icp_residuals: kfx_stage_icp_accumulate's inputs (CUR against PREV
+ * maps of `level` under the relative `pose`).  residual / label: w * h of that
+ * level; any of the three outputs may be NULL, not all.  DevState is not
+ * written: kfx_debug_get_icp_sums / kfx_debug_get_icp_step report what they
+ * did before.
+ * kfx_score_poses: the records of n relative poses in one launch (no per-pixel
+ * output); out[k] is kfx_stage_icp_residuals' record of poses[k].  A block
+ * walks kfx_quality_chunk(w, h, n) poses with its pixels in registers.  n = 0
+ * does no device work; n above 2^16 or a non-finite pose entry returns
+ * KFX_ERR_ARG with nothing written.
+ * kfx_frame_quality: kfx_stage_icp_residuals under the identity on the maps as
+ * they stand behind every queued frame: CUR, the measured maps of the last
+ * frame, against PREV, the model raycast from that frame's pose: how well the
+ * last frame sits on the model it was fused into.  kfx_stage_preprocess and
+ * kfx_slice_work* replace the CUR maps.  After a bootstrap frame PREV holds
+ * the measured maps (residuals 0); after a dropped frame what the reset left.
+ * kfx_score_view: the CUR maps of `level` against the volume seen from the
+ * world pose cam_pose: the model maps are kfx_render_view's vmap / nmap at
+ * that level's intrinsics (one direct raycast, no resize pyramid, with the pose
+ * in effect that kfx_render_view uses), then the identity relative pose.  The
+ * hypothesis test for relocalisation or for resuming on an uploaded volume.
+ * KFX_ERR_ARG on a non-finite pose entry, KFX_ERR_STATE on one slab of several.
+ * kfx_get_quality_ms: device ms (HIP events) of the last residual launch or
+ * batch [0] and of the view raycast in front of it [1] (0: there was none).
+ *
+ * All of them behave as kfx_render_view: on the context's stream behind every
+ * queued frame (staged and overlapped ones included), blocking until the data
+ * is on the host, writing only buffers of their own (grown on demand, freed in
+ * kfx_destroy), outside every captured graph, and a pending tracking status is
+ * left to the next kfx_synchronize.  All but kfx_score_view work on any slab
+ * context (the maps are replicated).  KFX_ERR_ARG: level outside 0..L-1, a
+ * null pose, every output null. */
+#define KFX_ICP_ACCEPT 0
+#define KFX_ICP_NAN 1
+#define KFX_ICP_PROJ 2
+#define KFX_ICP_DIST 3
+#define KFX_ICP_ANGLE 4
+#define KFX_ICP_UNCOVERED 5
+typedef struct kfx_icp_quality {
+  int64_t n[6];      /* pixels per label; they sum to the level's w*h */
+  int64_t sum_r2;    /* sum over accepted pixels of rint(RN(r*r) * 2^32): the sums' fixed point */
+  float   max_abs_r; /* max |r| over accepted pixels, 0 when there is none */
+  int32_t level;
+} kfx_icp_quality;   /* 64 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(kfx_icp_quality) == 64, "kfx_icp_quality is 64 bytes");
+#else
+_Static_assert(sizeof(kfx_icp_quality) == 64, "kfx_icp_quality is 64 bytes");
+#endif
+int kfx_stage_icp_residuals(kfx_ctx *ctx, int level, const kfx_pose *pose, float *residual, uint8_t *label,
+                            kfx_icp_quality *q);
+int kfx_score_poses(kfx_ctx *ctx, int level, const kfx_pose *poses, int64_t n, kfx_icp_quality *out);
+int kfx_frame_quality(kfx_ctx *ctx, int level, float *residual, uint8_t *label, kfx_icp_quality *q);
+int kfx_score_view(kfx_ctx *ctx, int level, const kfx_pose *cam_pose, float *residual, uint8_t *label,
+                   kfx_icp_quality *q);
+int kfx_get_quality_ms(kfx_ctx *ctx, float out_ms[2]);
+int kfx_quality_figures(const kfx_icp_quality *q, double *fitness, double *rmse);
+/* poses per block of a kfx_score_poses batch of n >= 1 at a w x h level: with
+ * pb = ceil(w * h / 1024) pixel blocks, clamp(n / ceil(512 / pb), 1, 16)
+ * (integer division): the most, up to 16, that leave a grid of 512 blocks. */
+int kfx_quality_chunk(int width, int height, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,14 @@ struct kfx_ctx {
   DevPose wv_pose{};
   hipEvent_t ev_wv[4]{};
   float wv_ms[2]{};
+  // ICP residuals and quality records.  Buffers of its own
+  // (grown on demand, kept, freed in kfx_destroy): [0] the poses, [1] the
+  // records, [2] residuals, [3] labels, [4] kfx_score_view's model maps
+  // [vmap | nmap].  Events: the view raycast [0, 1], the residual launch [2, 3].
+  void *q_buf[5]{};
+  size_t q_cap[5]{};
+  hipEvent_t ev_q[4]{};
+  float q_ms[2]{};
   uint8_t *mc_tab = nullptr;     // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded

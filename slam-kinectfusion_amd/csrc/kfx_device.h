@@ -1,6 +1,6 @@
 // kfx_device.h — device code that two or more of the kernel files
 // (kfx_kernels.hip, kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip,
-// kfx_shift.hip) use (the raycast march's functions: kfx_ray.h; the
+// kfx_shift.hip, kfx_quality.hip) use (the raycast march's functions: kfx_ray.h; the
 // extraction's per-voxel functions: kfx_extract_dev.h).  Everything lives
 // in an unnamed namespace: each file gets its own internal copy.  A helper with
 // one user lives in that file instead.

@@ -1255,4 +1255,139 @@ int kfx_shift_for_pose(const kfx_params *p, const kfx_pose *vp, const kfx_pose *
   return KFX_OK;
 }
 
+// ---- ICP residuals and quality records ---------------------
+
+// n poses of CUR level `level` against the model maps (pv, pn): the records,
+// and for one pose the per-pixel outcome.  On the frame stream behind every
+// queued frame; only q_buf is written; the pending tracking status is left
+// alone.  ev_q[2, 3] time the launch.
+static int quality_run(kfx_ctx *c, int level, const float *pv, const float *pn, const kfx_pose *poses, int64_t n,
+                       float *residual, uint8_t *label, kfx_icp_quality *out) {
+  int r;
+  const LevelGeom &g = c->g[level];
+  const size_t np = (size_t)g.w * g.h;
+  const bool store = residual || label;
+  if ((r = reserve(&c->q_buf[0], &c->q_cap[0], sizeof(DevPose) * (size_t)n, "quality"))) return r;
+  if ((r = reserve(&c->q_buf[1], &c->q_cap[1], sizeof(kfx_icp_quality) * (size_t)n, "quality"))) return r;
+  if (store && (r = reserve(&c->q_buf[2], &c->q_cap[2], 4 * np, "quality"))) return r;
+  if (store && (r = reserve(&c->q_buf[3], &c->q_cap[3], (np + 3) & ~(size_t)3, "quality"))) return r;
+  if ((r = make_events(c->ev_q, 4))) return r;
+  std::vector<DevPose> dp;
+  std::vector<kfx_icp_quality> rec;
+  try {
+    dp.resize((size_t)n);
+    rec.resize((size_t)n);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "quality: out of memory");
+  }
+  for (int64_t k = 0; k < n; ++k) dp[(size_t)k] = to_dev(poses[k]);
+  HIPCHK(hipMemcpyAsync(c->q_buf[0], dp.data(), sizeof(DevPose) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(c->q_buf[1], 0, sizeof(kfx_icp_quality) * (size_t)n, c->stream));
+  HIPCHK(hipEventRecord(c->ev_q[2], c->stream));
+  launch_quality(c->stream, g, c->cur.v[level], c->cur.n[level], pv, pn, c->p.icp_dist_threshold, c->angle_thr,
+                 static_cast<const DevPose *>(c->q_buf[0]), (int)n, c->q_buf[1], store ? (float *)c->q_buf[2] : nullptr,
+                 store ? (uint8_t *)c->q_buf[3] : nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_q[3], c->stream));
+  HIPCHK(hipMemcpyAsync(rec.data(), c->q_buf[1], sizeof(kfx_icp_quality) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (residual) HIPCHK(hipMemcpyAsync(residual, c->q_buf[2], 4 * np, hipMemcpyDeviceToHost, c->stream));
+  if (label) HIPCHK(hipMemcpyAsync(label, c->q_buf[3], np, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->q_ms[0], c->ev_q[2], c->ev_q[3]));
+  if (out)
+    for (int64_t k = 0; k < n; ++k) {
+      out[k] = rec[(size_t)k];
+      out[k].level = level;
+    }
+  return KFX_OK;
+}
+
+static int quality_args(kfx_ctx *c, int level, const void *a, const void *b, const void *q) {
+  if (level < 0 || level >= c->L) return set_err(KFX_ERR_ARG, "level outside 0..L-1");
+  if (!a && !b && !q) return set_err(KFX_ERR_ARG, "residual, label and record all null");
+  return KFX_OK;
+}
+
+int kfx_stage_icp_residuals(kfx_ctx *c, int level, const kfx_pose *pose, float *residual, uint8_t *label,
+                            kfx_icp_quality *q) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = quality_args(c, level, residual, label, q))) return r;
+  if (!pose) return set_err(KFX_ERR_ARG, "null pose");
+  c->q_ms[1] = 0.f;
+  return quality_run(c, level, c->prev.v[level], c->prev.n[level], pose, 1, residual, label, q);
+}
+
+int kfx_frame_quality(kfx_ctx *c, int level, float *residual, uint8_t *label, kfx_icp_quality *q) {
+  const kfx_pose id = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}};
+  return kfx_stage_icp_residuals(c, level, &id, residual, label, q);
+}
+
+int kfx_score_poses(kfx_ctx *c, int level, const kfx_pose *poses, int64_t n, kfx_icp_quality *out) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (level < 0 || level >= c->L) return set_err(KFX_ERR_ARG, "level outside 0..L-1");
+  if (n < 0 || n > 65536) return set_err(KFX_ERR_ARG, "n outside 0..2^16");
+  if (n == 0) return KFX_OK;
+  if (!poses || !out) return set_err(KFX_ERR_ARG, "null argument");
+  for (int64_t k = 0; k < n; ++k)
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(i < 9 ? poses[k].R[i] : poses[k].t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite pose entry");
+  c->q_ms[1] = 0.f;
+  return quality_run(c, level, c->prev.v[level], c->prev.n[level], poses, n, nullptr, nullptr, out);
+}
+
+int kfx_quality_chunk(int width, int height, int64_t n) {
+  if (width < 1 || height < 1 || n < 1 || (int64_t)width * height > ((int64_t)1 << 26))
+    return set_err(KFX_ERR_ARG, "quality_chunk: width, height, n >= 1 and width * height <= 2^26");
+  return quality_chunk(width, height, n);
+}
+
+int kfx_score_view(kfx_ctx *c, int level, const kfx_pose *cam_pose, float *residual, uint8_t *label,
+                   kfx_icp_quality *q) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = quality_args(c, level, residual, label, q))) return r;
+  if (!cam_pose) return set_err(KFX_ERR_ARG, "null pose");
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? cam_pose->R[i] : cam_pose->t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite view pose");
+  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "score_view on one slab of several");
+  const LevelGeom &g = c->g[level];
+  const size_t np = (size_t)g.w * g.h;
+  // [vmap | nmap | the view's image (k_view always stores one)]
+  if ((r = reserve(&c->q_buf[4], &c->q_cap[4], 27 * np, "score_view"))) return r;
+  if ((r = make_events(c->ev_q, 4))) return r;
+  float *dv = static_cast<float *>(c->q_buf[4]), *dn = dv + 3 * np;
+  const DevPose cam = to_dev(*cam_pose);
+  const DevPose c2v = host_pose_mul(host_pose_inv(to_dev(c->p.volu_pose)), cam);  // kfx_render_view's pose
+  HIPCHK(hipEventRecord(c->ev_q[0], c->stream));
+  launch_view(c->stream, c->vol, g, c2v, cam.t, KFX_VIEW_NORMAL, reinterpret_cast<uint8_t *>(dn + 3 * np), dv, dn,
+              nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_q[1], c->stream));
+  const kfx_pose id = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}};
+  if ((r = quality_run(c, level, dv, dn, &id, 1, residual, label, q))) return r;
+  HIPCHK(hipEventElapsedTime(&c->q_ms[1], c->ev_q[0], c->ev_q[1]));
+  return KFX_OK;
+}
+
+int kfx_get_quality_ms(kfx_ctx *c, float out_ms[2]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  out_ms[0] = c->q_ms[0];
+  out_ms[1] = c->q_ms[1];
+  return KFX_OK;
+}
+
+int kfx_quality_figures(const kfx_icp_quality *q, double *fitness, double *rmse) {
+  if (!q || !fitness || !rmse) return set_err(KFX_ERR_ARG, "null argument");
+  for (int k = 0; k < 6; ++k)
+    if (q->n[k] < 0) return set_err(KFX_ERR_ARG, "negative count");
+  const int64_t den = q->n[0] + q->n[2] + q->n[3] + q->n[4];
+  *fitness = den ? (double)q->n[0] / (double)den : 0.0;
+  *rmse = q->n[0] ? std::sqrt(((double)q->sum_r2 / 4294967296.0) / (double)q->n[0]) : 0.0;
+  return KFX_OK;
+}
+
 }  // extern "C"

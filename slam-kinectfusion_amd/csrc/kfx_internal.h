@@ -1,5 +1,5 @@
 // kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip,
-// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip, kfx_world_view.hip) and the host runtime (kfx_api.hip, kfx_export.hip).  Not part of the public ABI.
+// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip, kfx_world_view.hip, kfx_quality.hip) and the host runtime (kfx_api.hip, kfx_export.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -409,6 +409,19 @@ void launch_render(hipStream_t s, const float *vmap, const float *nmap, int n, c
 // vmap / nmap (float3) and ts (Ts of the hit, 0: none) are stored when non-null
 void launch_view(hipStream_t s, VolView v, LevelGeom g, DevPose cam2vol, const float eye[3], int type, uint8_t *out,
                  float *vmap, float *nmap, float *ts);
+
+// ---- kfx_quality.hip ------------------------------------------------------
+// the ICP residual map and quality records: CUR maps (cv, cn)
+// against model maps (pv, pn) of geometry g under each of the n relative poses
+// (device array).  rec: n zeroed 64-byte kfx_icp_quality records the launch
+// adds into.  residual / label (both or neither; w * h floats / bytes, n = 1):
+// the per-pixel outcome.  Without them the poses go quality_chunk(w, h, n) to a
+// block: the most, up to 16, that still leave 512 blocks (pixel blocks of 1024
+// x chunks), at least 1.
+int quality_chunk(int w, int h, long long n);
+void launch_quality(hipStream_t s, const LevelGeom &g, const float *cv, const float *cn, const float *pv, const float *pn,
+                    float dist_thr, float angle_thr, const DevPose *poses, int n, void *rec, float *residual,
+                    uint8_t *label);
 
 // ---- kfx_shift.hip --------------------------------------------------------
 // the moving volume, whole single volumes only.  shift: voxels

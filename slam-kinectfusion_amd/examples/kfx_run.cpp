@@ -20,10 +20,14 @@
 // kfx_save_world_mesh_indexed; a twelfth, with the eighth, world_view.ppm, DESIGN.md
 // §25: window plus store in fused colour, seen from the first recorded pose
 // through the dataset's intrinsics, kfx_save_world_view: the whole map, also
-// where the window has moved on).
+// where the window has moved on; a thirteenth names a text file that gets one
+// line per processed frame, DESIGN.md §26: frame index, kfx_pipeline's status,
+// the six label counts at level 0, fitness and rmse of kfx_frame_quality after
+// the frame).  An empty name skips its output, the followed cloud's included,
+// so that a later argument can be given alone.
 //   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
 //                  [followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply]
-//                  [world_view.ppm]
+//                  [world_view.ppm] [quality.txt]
 #include <chrono>
 #include <cstdio>
 #include <vector>
@@ -35,7 +39,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr,
                  "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm] "
                  "[followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply] "
-                 "[world_view.ppm]\n",
+                 "[world_view.ppm] [quality.txt]\n",
                  argv[0]);
     return 2;
   }
@@ -63,7 +67,7 @@ int main(int argc, char **argv) {
   std::vector<uint8_t> bgr((size_t)intr.width * intr.height * 3);
   std::vector<float> depth((size_t)intr.width * intr.height);
   double gpu_s = 0;
-  const bool follow = argc > 7;  // the volume follows the camera
+  const bool follow = argc > 7 && argv[7][0];  // the volume follows the camera
   const float ahead = 0.5f + p.volu_range[2] / 2;
   std::vector<kfx_vertex> evicted;
   int shifts = 0;
@@ -74,6 +78,11 @@ int main(int argc, char **argv) {
   long long bricks_out = 0, bricks_in = 0;
   if (stream && kfx_brick_store_create(&store) != KFX_OK) {
     std::fprintf(stderr, "error: %s\n", kfx_last_error());
+    return 1;
+  }
+  std::FILE *qlog = nullptr;  // per-frame tracking quality
+  if (argc > 13 && argv[13][0] && !(qlog = std::fopen(argv[13], "w"))) {
+    std::fprintf(stderr, "error: cannot open %s\n", argv[13]);
     return 1;
   }
   for (int k = 0; k < n; ++k) {
@@ -89,6 +98,16 @@ int main(int argc, char **argv) {
     } else if (r != KFX_OK) {
       std::fprintf(stderr, "error: %s\n", kfx_last_error());
       return 1;
+    }
+    if (qlog) {  // how well the frame sits on the model it was fused into
+      kfx_icp_quality q;
+      double fitness = 0, rmse = 0;
+      if (kfx_frame_quality(ctx, 0, nullptr, nullptr, &q) != KFX_OK || kfx_quality_figures(&q, &fitness, &rmse) != KFX_OK) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      std::fprintf(qlog, "%d %d %lld %lld %lld %lld %lld %lld %.9g %.9g\n", k, r, (long long)q.n[0], (long long)q.n[1],
+                   (long long)q.n[2], (long long)q.n[3], (long long)q.n[4], (long long)q.n[5], fitness, rmse);
     }
     if (!follow) continue;
     if (r == KFX_TRACKING_LOST) {  // the device reset cannot move the volume back: kfx.h (the store is kept)
@@ -249,6 +268,7 @@ int main(int argc, char **argv) {
     std::printf("streamed: %lld bricks out, %lld back in, %lld held\n", bricks_out, bricks_in, (long long)held);
     kfx_brick_store_destroy(store);
   }
+  if (qlog) std::fclose(qlog);
   std::printf("end! %d frames, frame_count %d, %.3f ms/frame in kfx_pipeline (host frames, PCIe incl.)\n", n,
               frames, n ? 1e3 * gpu_s / n : 0.0);
   kfx_destroy(ctx);

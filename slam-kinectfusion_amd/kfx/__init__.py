@@ -15,12 +15,12 @@ import subprocess
 
 import numpy as np
 
-from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, Intrinsics, Params, Pose,
+from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, IcpQuality, Intrinsics, Params, Pose,
                   default_params, fptr, i16ptr, i64ptr, u8ptr, u16ptr)
 
 __all__ = ["KinectFusion", "KfxError", "Dataset", "png_info", "png_read_bgr8", "png_read_depth", "parse_intr",
            "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "write_ply_attr", "write_ply_mesh_attr",
-           "write_ply_mesh_indexed", "write_ppm", "shift_for_pose", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
+           "write_ply_mesh_indexed", "write_ppm", "shift_for_pose", "quality_figures", "quality_chunk", "IcpQuality", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
            "default_params", "KFX_FRAME_CUR", "KFX_FRAME_PREV", "KFX_OK", "KFX_TRACKING_LOST", "EXPORTS"]
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,6 +52,8 @@ EXPORTS = [
     "kfx_debug_count_settled", "kfx_debug_get_settled", "kfx_debug_get_hidden", "kfx_debug_int_tiles",
     "kfx_debug_get_icp_sums", "kfx_debug_cap_icp_blocks", "kfx_debug_extract_units", "kfx_debug_scan",
     "kfx_debug_get_icp_step",
+    "kfx_stage_icp_residuals", "kfx_score_poses", "kfx_frame_quality", "kfx_score_view", "kfx_get_quality_ms",
+    "kfx_quality_figures", "kfx_quality_chunk",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
 ]
@@ -201,6 +203,13 @@ def lib():
         "kfx_write_ply_mesh_attr": ([C.c_char_p, vp, C.c_int64], i),
         "kfx_save_pointcloud_attr": ([vp, C.c_char_p, C.c_int64], i),
         "kfx_save_mesh_attr": ([vp, C.c_char_p, C.c_int64], i),
+        "kfx_stage_icp_residuals": ([vp, i, P(Pose), P(f), P(C.c_uint8), P(IcpQuality)], i),
+        "kfx_score_poses": ([vp, i, P(Pose), C.c_int64, P(IcpQuality)], i),
+        "kfx_frame_quality": ([vp, i, P(f), P(C.c_uint8), P(IcpQuality)], i),
+        "kfx_score_view": ([vp, i, P(Pose), P(f), P(C.c_uint8), P(IcpQuality)], i),
+        "kfx_get_quality_ms": ([vp, P(f)], i),
+        "kfx_quality_figures": ([P(IcpQuality), P(C.c_double), P(C.c_double)], i),
+        "kfx_quality_chunk": ([i, i, C.c_int64], i),
         "kfx_dataset_open": ([C.c_char_p, P(vp)], i),
         "kfx_dataset_info": ([vp, P(Intrinsics), P(i), P(i)], i),
         "kfx_dataset_read": ([vp, i, P(C.c_uint8), P(f)], i),
@@ -266,6 +275,19 @@ def write_ppm(path: str, bgr: np.ndarray):
     assert img.ndim == 3 and img.shape[2] == 3
     _check(lib().kfx_write_ppm(path.encode(), img.ctypes.data_as(C.POINTER(C.c_uint8)), img.shape[1], img.shape[0]),
            "kfx_write_ppm")
+
+
+def quality_figures(q: IcpQuality) -> tuple:
+    """kfx_quality_figures: (fitness, rmse) of a record, both float (host only)."""
+    a, b = C.c_double(), C.c_double()
+    _check(lib().kfx_quality_figures(C.byref(q), C.byref(a), C.byref(b)), "kfx_quality_figures")
+    return a.value, b.value
+
+
+def quality_chunk(width: int, height: int, n: int) -> int:
+    """kfx_quality_chunk: poses one block of a score_poses batch of n walks at a width x height level."""
+    return _check(lib().kfx_quality_chunk(int(width), int(height), int(n)), "kfx_quality_chunk",
+                  ok=range(1, 17))
 
 
 def shift_for_pose(params: Params, volume_pose, cam_pose, ahead_m: float) -> tuple:
@@ -799,6 +821,46 @@ class KinectFusion:
         ms = C.c_float()
         _check(lib().kfx_get_view_ms(self._h, C.byref(ms)), "kfx_get_view_ms")
         return float(ms.value)
+
+    # ---- ICP residuals and tracking quality ----------------
+    def _quality(self, name: str, level: int, args: tuple, maps: bool):
+        g = self.intr.level(level)
+        res = np.zeros((g.height, g.width), np.float32) if maps else None
+        lab = np.zeros((g.height, g.width), np.uint8) if maps else None
+        q = IcpQuality()
+        _check(getattr(lib(), name)(self._h, int(level), *args, fptr(res) if maps else None,
+                                    u8ptr(lab) if maps else None, C.byref(q)), name)
+        return (q, res, lab) if maps else q
+
+    def stage_icp_residuals(self, level: int, pose, maps: bool = True):
+        """kfx_stage_icp_residuals: CUR against PREV maps of `level` under the
+        relative `pose`.  Returns (IcpQuality, residual (h, w) float32, label
+        (h, w) uint8), or with maps=False the record alone (no per-pixel stores)."""
+        P = pose if isinstance(pose, Pose) else Pose.from_matrix(pose)
+        return self._quality("kfx_stage_icp_residuals", level, (C.byref(P),), maps)
+
+    def frame_quality(self, level: int = 0, maps: bool = False):
+        """kfx_frame_quality: the last frame's maps against the model raycast from its pose (identity)."""
+        return self._quality("kfx_frame_quality", level, (), maps)
+
+    def score_view(self, level: int, cam_pose, maps: bool = False):
+        """kfx_score_view: CUR maps of `level` against the volume seen from the world pose cam_pose."""
+        P = cam_pose if isinstance(cam_pose, Pose) else Pose.from_matrix(cam_pose)
+        return self._quality("kfx_score_view", level, (C.byref(P),), maps)
+
+    def score_poses(self, level: int, poses) -> list:
+        """kfx_score_poses: one IcpQuality per relative pose (Pose or 4x4), one launch."""
+        ps = [p if isinstance(p, Pose) else Pose.from_matrix(p) for p in poses]
+        arr = (Pose * max(len(ps), 1))(*ps)
+        out = (IcpQuality * max(len(ps), 1))()
+        _check(lib().kfx_score_poses(self._h, int(level), arr, len(ps), out), "kfx_score_poses")
+        return list(out)[:len(ps)]
+
+    def quality_ms(self) -> dict:
+        """Device ms of the last residual launch or batch, and of the view raycast in front of it (0: none)."""
+        a = (C.c_float * 2)()
+        _check(lib().kfx_get_quality_ms(self._h, a), "kfx_get_quality_ms")
+        return {"residuals": float(a[0]), "view": float(a[1])}
 
     # ---- moving volume (DESIGN.md §20) ------------------------------------
     def shift_volume(self, shift):

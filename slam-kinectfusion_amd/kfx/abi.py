@@ -67,6 +67,14 @@ class Params(C.Structure):
                 ("tsdf_max_weight", C.c_int), ("min_pose_move", C.c_float)]
 
 
+class IcpQuality(C.Structure):
+    """kfx_icp_quality (64 bytes): pixels per label, the fixed-point sum of r^2, max |r|, the level."""
+    _fields_ = [("n", C.c_int64 * 6), ("sum_r2", C.c_int64), ("max_abs_r", C.c_float), ("level", C.c_int32)]
+
+    def fields(self) -> tuple:
+        return tuple(self.n[:]) + (int(self.sum_r2), float(self.max_abs_r), int(self.level))
+
+
 def default_params(dims: int = 512, range_m: float = 3.0) -> Params:
     """kinectfuison_params::default_params (kinectfusion.cpp:167-190), with the
     volume size/range overridable (BASELINE configs use 4 mm / 2 mm voxels)."""
