@@ -991,6 +991,78 @@ int kfx_quality_figures(const kfx_icp_quality *q, double *fitness, double *rmse)
  * (integer division): the most, up to 16, that leave a grid of 512 blocks. */
 int kfx_quality_chunk(int width, int height, int64_t n);
 
+/* ---- multi-start ICP, tracking against a view, resuming at a pose
+ * Added under ABI version 2, nothing else changed.  The tracker's coarse-to-fine
+ * loop (ICPRegistration::rigidTransform, icp_registration.cpp:16-46: levels
+ * L-1 .. 0, icp_iter_count[level] iterations each, the context's thresholds)
+ * from each of n start poses instead of the identity, all n in one launch per
+ * (level, iteration): 19 launches at the defaults whatever n is.  Each pose
+ * runs kfx_stage_icp's arithmetic (exact int64 sums, the 3+3 block solve with
+ * its determinant test, Rodrigues, pose = pose * Tinc), so out[k] is bit for
+ * bit what the loop gives from starts[k], whatever the batch around it.  A
+ * pose whose solve fails the determinant test stops there: status
+ * KFX_TRACKING_LOST, (stop_level, stop_iter) the failing solve, pose the one
+ * reached before it; the others go on.
+ *
+ * kfx_icp_multi: CUR against the PREV maps as they stand (kfx_stage_icp's
+ * inputs).  n in 0..2^16; n = 0 returns KFX_OK and touches nothing.
+ * KFX_ERR_ARG, with nothing written: n outside that, a null starts or out, a
+ * non-finite pose entry.  q (may be NULL): n records, out[k].pose scored at
+ * level 0 on the same model maps (kfx_score_poses' record; a lost pose is
+ * scored where it stopped).
+ * kfx_track_view: the same loop against the volume seen from the world pose
+ * cam_pose.  The model maps are a pyramid of the call's own: at every level
+ * one direct raycast at that level's intrinsics (kfx_score_view's maps of that
+ * level, not the resize pyramid).  world (may be NULL): world[k] = cam_pose *
+ * out[k].pose, the camera's world pose, composed on the host in float32 in
+ * the order of the tracker's pose product.  KFX_ERR_ARG also on a null or
+ * non-finite cam_pose; KFX_ERR_STATE on one slab of several.
+ * kfx_icp_multi_chunk (host only, no context): poses one block walks in a
+ * batch of n >= 1 at a w x h level: with pb = max(1, ceil(xe * ye / 1024))
+ * pixel blocks of the floor-covered region (xe = (w/32)*32, ye = (h/32)*32),
+ * clamp(n / ceil(512 / pb), 1, 16) (integer division).  Results do not depend
+ * on it.
+ * kfx_get_icp_multi_ms: device ms (HIP events) of the last call: the view
+ * raycasts [0] (0: kfx_icp_multi), the loop's launches [1], the scoring [2]
+ * (0: q was NULL).
+ *
+ * Both calls behave as kfx_render_view and kfx_score_poses: on the context's
+ * stream behind every queued frame, blocking, writing only buffers of their
+ * own (grown on demand, freed in kfx_destroy), outside every captured graph;
+ * DevState is not written (kfx_debug_get_icp_sums / kfx_debug_get_icp_step
+ * report what they did before) and a pending tracking status is left to the
+ * next kfx_synchronize.
+ *
+ * kfx_resume_at: the next frame tracks from the world pose cam_pose against
+ * the volume as it stands (after kfx_upload_tsdf on a fresh context: resume on
+ * a restored volume).  Waits for every queued frame, appends cam_pose to the
+ * pose record (KFX_ERR_STATE when the record is full), sets the frame count to
+ * max(frame count, 1) + 1 so that the next frame tracks instead of
+ * bootstrapping, and writes the PREV maps a frame tracked at cam_pose would
+ * have left: kfx_stage_raycast at cam2vol = inv(volume pose in effect) *
+ * cam_pose with the resize pyramid.  Holds in every graph mode, with frame
+ * overlap on or off.  KFX_ERR_ARG on a null or non-finite pose, KFX_ERR_STATE
+ * on one slab of several.  The only call of this section that writes tracker
+ * state; a pending tracking status is left to the next kfx_synchronize. */
+typedef struct kfx_icp_result {
+  kfx_pose pose;      /* relative pose reached (the start, if no solve succeeded) */
+  int32_t status;     /* KFX_OK or KFX_TRACKING_LOST */
+  int32_t stop_level, stop_iter; /* the failing solve; -1, -1 when status is KFX_OK */
+  int32_t solves;     /* solves that succeeded */
+  double x[6];        /* last successful solve's increment; zeros if none */
+} kfx_icp_result;     /* 112 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(kfx_icp_result) == 112, "kfx_icp_result is 112 bytes");
+#else
+_Static_assert(sizeof(kfx_icp_result) == 112, "kfx_icp_result is 112 bytes");
+#endif
+int kfx_icp_multi(kfx_ctx *ctx, const kfx_pose *starts, int64_t n, kfx_icp_result *out, kfx_icp_quality *q);
+int kfx_track_view(kfx_ctx *ctx, const kfx_pose *cam_pose, const kfx_pose *starts, int64_t n, kfx_icp_result *out,
+                   kfx_pose *world, kfx_icp_quality *q);
+int kfx_resume_at(kfx_ctx *ctx, const kfx_pose *cam_pose);
+int kfx_icp_multi_chunk(int width, int height, int64_t n);
+int kfx_get_icp_multi_ms(kfx_ctx *ctx, float out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,39 @@ class kinectfusion {
     if (kfx_save_world_view(ctx_, store, &ci, &p, KFX_VIEW_COLOR, path.c_str()) != KFX_OK)
       throw std::runtime_error(kfx_last_error());
   }
+  // Extensions (kfx_icp_multi, kfx_track_view, kfx_resume_at).  trackFrom: the
+  // tracker's coarse-to-fine loop for the last frame from every relative start
+  // pose, one batch.  trackView: the same against the volume seen from the
+  // world pose `view`; world (optional) receives view * the pose reached, per
+  // start.  resumeAt: the next frame tracks from `pose` against the volume as
+  // it stands (after an upload into a fresh instance).
+  std::vector<kfx_icp_result> trackFrom(const std::vector<cv::Affine3f> &starts) {
+    std::vector<kfx_pose> s;
+    for (const cv::Affine3f &a : starts) s.push_back(to_kfx(a));
+    std::vector<kfx_icp_result> out(s.size());
+    if (kfx_icp_multi(ctx_, s.data(), (int64_t)s.size(), out.data(), nullptr) != KFX_OK)
+      throw std::runtime_error(kfx_last_error());
+    return out;
+  }
+  std::vector<kfx_icp_result> trackView(const cv::Affine3f &view, const std::vector<cv::Affine3f> &starts,
+                                        std::vector<cv::Affine3f> *world = nullptr) {
+    const kfx_pose v = to_kfx(view);
+    std::vector<kfx_pose> s, w(starts.size());
+    for (const cv::Affine3f &a : starts) s.push_back(to_kfx(a));
+    std::vector<kfx_icp_result> out(s.size());
+    if (kfx_track_view(ctx_, &v, s.data(), (int64_t)s.size(), out.data(), w.data(), nullptr) != KFX_OK)
+      throw std::runtime_error(kfx_last_error());
+    if (world) {
+      world->clear();
+      for (const kfx_pose &p : w) world->push_back(from_kfx(p));
+    }
+    return out;
+  }
+  void resumeAt(const cv::Affine3f &pose) {
+    const kfx_pose p = to_kfx(pose);
+    if (kfx_resume_at(ctx_, &p) != KFX_OK) throw std::runtime_error(kfx_last_error());
+    sync_host_state();
+  }
   cv::Affine3f getCurCameraPose() { return pose_record.back(); }
   void release() {
     if (ctx_) kfx_destroy(ctx_);

@@ -206,7 +206,16 @@ struct kfx_ctx {
   size_t q_cap[5]{};
   hipEvent_t ev_q[4]{};
   float q_ms[2]{};
-  uint8_t *mc_tab = nullptr;     // marching-cubes table (uploaded on first use)
+  // multi-start ICP.  Buffers of its own (grown on demand,
+  // kept, freed in kfx_destroy): [0] the batch's poses (IcpMultiPose), [1] their
+  // sum rows and tickets, [2] kfx_track_view's model pyramid, per level
+  // [vmap | nmap | the view's image].  Events: the view raycasts [0, 1], the
+  // iterations' launches [2, 3].  m_ms: raycasts, loop, final scoring.
+  void *m_buf[3]{};
+  size_t m_cap[3]{};
+  hipEvent_t ev_m[4]{};
+  float m_ms[3]{};
+  uint8_t *mc_tab = nullptr;    // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded
   // march left unexamined, and the hit payload

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "kfx_ctx.h"
+#include "kfx_multi.h"
 #include "kfx_scanws.h"
 
 namespace {
@@ -276,16 +277,7 @@ extern "C" {
 // this file is built without contraction, so the host sums round the same.
 static DevPose host_pose_mul(const DevPose &a, const DevPose &b) {
   DevPose r;
-  for (int j = 0; j < 3; ++j) {
-    for (int i = 0; i < 3; ++i) {
-      float v = 0.f;
-      for (int k = 0; k < 3; ++k) v += a.R[3 * j + k] * b.R[3 * k + i];
-      r.R[3 * j + i] = v;
-    }
-    float d = 0.f;
-    for (int k = 0; k < 3; ++k) d += a.R[3 * j + k] * b.t[k];
-    r.t[j] = d + a.t[j];
-  }
+  pose_mul_f32(a.R, a.t, b.R, b.t, r.R, r.t);  // (kfx_multi.h: the same loops, where a host check can build them)
   return r;
 }
 static DevPose host_pose_inv(const DevPose &a) {
@@ -1388,6 +1380,184 @@ int kfx_quality_figures(const kfx_icp_quality *q, double *fitness, double *rmse)
   *fitness = den ? (double)q->n[0] / (double)den : 0.0;
   *rmse = q->n[0] ? std::sqrt(((double)q->sum_r2 / 4294967296.0) / (double)q->n[0]) : 0.0;
   return KFX_OK;
+}
+
+// ---- multi-start ICP ----------------------------------------
+
+static_assert(sizeof(IcpMultiPose) == sizeof(kfx_icp_result) && offsetof(IcpMultiPose, x) == offsetof(kfx_icp_result, x) &&
+                  offsetof(IcpMultiPose, fail) == offsetof(kfx_icp_result, status),
+              "the device record is the public one");
+
+// the argument checks kfx_icp_multi and kfx_track_view share (n > 0 behind them)
+static int multi_args(const kfx_pose *starts, int64_t n, const kfx_icp_result *out) {
+  if (n < 0 || n > 65536) return set_err(KFX_ERR_ARG, "n outside 0..2^16");
+  if (n == 0) return KFX_OK;
+  if (!starts || !out) return set_err(KFX_ERR_ARG, "null argument");
+  for (int64_t k = 0; k < n; ++k)
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(i < 9 ? starts[k].R[i] : starts[k].t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite pose entry");
+  return KFX_OK;
+}
+
+// ICPRegistration::rigidTransform's loop from each of n starts, CUR against the
+// model maps (pv, pn) of every level: one launch per (level, iteration).  On
+// the frame stream behind every queued frame; only m_buf[0, 1] are written; the
+// pending tracking status is left alone.  ev_m[2, 3] time the launches.  With
+// q, the poses reached are scored at level 0 on the same maps (quality_run;
+// kfx_get_quality_ms reads as before).
+static int multi_run(kfx_ctx *c, const float *const *pv, const float *const *pn, const kfx_pose *starts, int64_t n,
+                     kfx_icp_result *out, kfx_icp_quality *q) {
+  int r;
+  const size_t rows = sizeof(unsigned long long) * 27 * (size_t)n;
+  if ((r = reserve(&c->m_buf[0], &c->m_cap[0], sizeof(IcpMultiPose) * (size_t)n, "icp_multi"))) return r;
+  if ((r = reserve(&c->m_buf[1], &c->m_cap[1], rows + sizeof(unsigned) * (size_t)n, "icp_multi"))) return r;
+  if ((r = make_events(c->ev_m, 4))) return r;
+  std::vector<IcpMultiPose> mp;
+  try {
+    mp.resize((size_t)n);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "icp_multi: out of memory");
+  }
+  for (int64_t k = 0; k < n; ++k) {
+    IcpMultiPose &m = mp[(size_t)k];
+    std::memset(&m, 0, sizeof(m));
+    m.pose = to_dev(starts[k]);
+    m.stop_level = m.stop_iter = -1;
+  }
+  IcpMultiPose *dp = static_cast<IcpMultiPose *>(c->m_buf[0]);
+  unsigned long long *drows = static_cast<unsigned long long *>(c->m_buf[1]);
+  unsigned *dtick = reinterpret_cast<unsigned *>(drows + 27 * (size_t)n);
+  HIPCHK(hipMemcpyAsync(dp, mp.data(), sizeof(IcpMultiPose) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(drows, 0, rows + sizeof(unsigned) * (size_t)n, c->stream));
+  HIPCHK(hipEventRecord(c->ev_m[2], c->stream));
+  for (int level = c->L - 1; level >= 0; --level)
+    for (int it = 0; it < c->p.icp_iter_count[level]; ++it)
+      launch_icp_multi(c->stream, c->g[level], c->cur.v[level], c->cur.n[level], pv[level], pn[level],
+                       c->p.icp_dist_threshold, c->angle_thr, dp, (int)n, drows, dtick, level, it);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_m[3], c->stream));
+  HIPCHK(hipMemcpyAsync(mp.data(), dp, sizeof(IcpMultiPose) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->m_ms[1], c->ev_m[2], c->ev_m[3]));
+  c->m_ms[2] = 0.f;
+  for (int64_t k = 0; k < n; ++k) {
+    const IcpMultiPose &m = mp[(size_t)k];
+    kfx_icp_result &o = out[k];
+    o.pose = to_api(m.pose);
+    o.status = m.fail ? KFX_TRACKING_LOST : KFX_OK;
+    o.stop_level = m.stop_level;
+    o.stop_iter = m.stop_iter;
+    o.solves = m.solves;
+    std::memcpy(o.x, m.x, sizeof(o.x));
+  }
+  if (q) {
+    std::vector<kfx_pose> reached;
+    try {
+      reached.resize((size_t)n);
+    } catch (const std::bad_alloc &) {
+      return set_err(KFX_ERR_OOM, "icp_multi: out of memory");
+    }
+    for (int64_t k = 0; k < n; ++k) reached[(size_t)k] = out[k].pose;
+    const float keep = c->q_ms[0];
+    r = quality_run(c, 0, pv[0], pn[0], reached.data(), n, nullptr, nullptr, q);
+    c->m_ms[2] = c->q_ms[0];
+    c->q_ms[0] = keep;
+    if (r) return r;
+  }
+  return KFX_OK;
+}
+
+int kfx_icp_multi(kfx_ctx *c, const kfx_pose *starts, int64_t n, kfx_icp_result *out, kfx_icp_quality *q) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = multi_args(starts, n, out)) || n == 0) return r;
+  c->m_ms[0] = 0.f;
+  return multi_run(c, c->prev.v, c->prev.n, starts, n, out, q);
+}
+
+int kfx_track_view(kfx_ctx *c, const kfx_pose *cam_pose, const kfx_pose *starts, int64_t n, kfx_icp_result *out,
+                   kfx_pose *world, kfx_icp_quality *q) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!cam_pose) return set_err(KFX_ERR_ARG, "null pose");
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? cam_pose->R[i] : cam_pose->t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite view pose");
+  if ((r = multi_args(starts, n, out)) || n == 0) return r;
+  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "track_view on one slab of several");
+  // the model pyramid: per level [vmap | nmap | the view's image (k_view always stores one)], one direct
+  // raycast each at that level's intrinsics (kfx_score_view's, not the resize pyramid)
+  size_t off[kMaxLevels + 1] = {0};
+  for (int l = 0; l < c->L; ++l) off[l + 1] = off[l] + ((27 * (size_t)c->g[l].w * c->g[l].h + 15) & ~(size_t)15);
+  if ((r = reserve(&c->m_buf[2], &c->m_cap[2], off[c->L], "track_view"))) return r;
+  if ((r = make_events(c->ev_m, 4))) return r;
+  const DevPose cam = to_dev(*cam_pose);
+  const DevPose c2v = host_pose_mul(host_pose_inv(to_dev(c->p.volu_pose)), cam);  // kfx_render_view's pose
+  const float *pv[kMaxLevels] = {}, *pn[kMaxLevels] = {};
+  HIPCHK(hipEventRecord(c->ev_m[0], c->stream));
+  for (int l = 0; l < c->L; ++l) {
+    const size_t np = (size_t)c->g[l].w * c->g[l].h;
+    float *dv = reinterpret_cast<float *>(static_cast<char *>(c->m_buf[2]) + off[l]), *dn = dv + 3 * np;
+    launch_view(c->stream, c->vol, c->g[l], c2v, cam.t, KFX_VIEW_NORMAL, reinterpret_cast<uint8_t *>(dn + 3 * np), dv, dn,
+                nullptr);
+    pv[l] = dv;
+    pn[l] = dn;
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_m[1], c->stream));
+  if ((r = multi_run(c, pv, pn, starts, n, out, q))) return r;
+  HIPCHK(hipEventElapsedTime(&c->m_ms[0], c->ev_m[0], c->ev_m[1]));
+  if (world)
+    for (int64_t k = 0; k < n; ++k) world[k] = to_api(host_pose_mul(cam, to_dev(out[k].pose)));
+  return KFX_OK;
+}
+
+int kfx_icp_multi_chunk(int width, int height, int64_t n) {
+  if (width < 1 || height < 1 || n < 1 || (int64_t)width * height > ((int64_t)1 << 26))
+    return set_err(KFX_ERR_ARG, "icp_multi_chunk: width, height, n >= 1 and width * height <= 2^26");
+  return icp_multi_chunk(width, height, n);
+}
+
+int kfx_get_icp_multi_ms(kfx_ctx *c, float out_ms[3]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  for (int k = 0; k < 3; ++k) out_ms[k] = c->m_ms[k];
+  return KFX_OK;
+}
+
+// The next frame tracks from cam_pose against the volume as it stands: the
+// pose joins the record, the frame count leaves the bootstrap, and PREV is what
+// a frame tracked at cam_pose would have left (kfx_stage_raycast at cam2vol =
+// inv(volume pose) * cam_pose, Rinv = its rotation transposed).  The captured
+// graphs read the record, the count and PREV from device memory at the
+// addresses they hold, none of which moves here, so they stay.
+int kfx_resume_at(kfx_ctx *c, const kfx_pose *cam_pose) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!cam_pose) return set_err(KFX_ERR_ARG, "null pose");
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? cam_pose->R[i] : cam_pose->t[i - 9])) return set_err(KFX_ERR_ARG, "non-finite pose entry");
+  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "resume_at on one slab of several");
+  if (c->cstream) HIPCHK(hipStreamSynchronize(c->cstream));
+  HIPCHK(hipStreamSynchronize(c->pstream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  DevState s;
+  HIPCHK(hipMemcpy(&s, c->st, sizeof(s), hipMemcpyDeviceToHost));
+  if (s.n_poses >= c->pose_cap) return set_err(KFX_ERR_STATE, "resume_at: the pose record is full");
+  const DevPose cam = to_dev(*cam_pose);
+  HIPCHK(hipMemcpy(c->pose_log + s.n_poses, &cam, sizeof(cam), hipMemcpyHostToDevice));
+  // the state's head, frame_count .. n_poses, as read (nothing runs that could write it), in one copy
+  static_assert(offsetof(DevState, frame_count) == 0 && offsetof(DevState, n_poses) == 3 * sizeof(int), "the head");
+  s.n_poses += 1;
+  s.frame_count = std::max(s.frame_count, 1) + 1;
+  HIPCHK(hipMemcpy(c->st, &s, 4 * sizeof(int), hipMemcpyHostToDevice));
+  c->known_poses = s.n_poses;  // every queued frame has completed (the pending status is left to kfx_synchronize)
+  const DevPose c2v = host_pose_mul(host_pose_inv(to_dev(c->p.volu_pose)), cam);  // tsdf_volume.cpp:59
+  const kfx_pose cam2vol = to_api(c2v);
+  float Rinv[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) Rinv[3 * i + j] = c2v.R[3 * j + i];
+  return kfx_stage_raycast(c, &cam2vol, Rinv);
 }
 
 }  // extern "C"

@@ -292,6 +292,21 @@ void launch_icp(hipStream_t s, const LevelGeom &g, const float *cv, const float 
                 int nbands = 1);
 // one ICP solve (+ pose update) from DevState::sums
 void launch_icp_solve(hipStream_t s, DevState *st);
+// Multi-start ICP.  One pose of a batch, as the device keeps it
+// between the iterations' launches: the layout of the public kfx_icp_result
+// (fail: 0, or 1 once a solve failed the determinant test at (stop_level, stop_iter)).
+struct IcpMultiPose {
+  DevPose pose;
+  int fail, stop_level, stop_iter, solves;
+  double x[6];
+};
+// poses one block of a batch of n walks at a w x h level: quality_chunk's rule on the ICP's pixel blocks
+int icp_multi_chunk(int w, int h, long long n);
+// one ICP iteration (launch_icp's, with the solve) of every pose of the batch that has not failed, in one
+// launch.  rows: n x 27 int64, tickets: n words, all zero (each pose's last block restores that).
+void launch_icp_multi(hipStream_t s, const LevelGeom &g, const float *cv, const float *cn, const float *pv,
+                      const float *pn, float dist_thr, float angle_thr, IcpMultiPose *poses, int n,
+                      unsigned long long *rows, unsigned *tickets, int level, int iter);
 // DevState::sums of each of the n members <- their sum
 void launch_group_sum_icp(hipStream_t s, DevState *const *st, int n);
 // The frame's global pose, the integrate/raycast poses and the

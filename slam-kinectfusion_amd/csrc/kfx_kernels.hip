@@ -18,6 +18,7 @@
 #include "kfx_ffadd.h"
 #include "kfx_raystep.h"
 #include "kfx_settled.h"
+#include "kfx_multi.h"
 #include "kfx_sqrtbound.h"
 #include "kfx_tilemask.h"
 
@@ -3607,6 +3608,109 @@ void launch_host_fetch(hipStream_t s, const void *src0, void *dst0, size_t n0, c
 void launch_inv_lambda(hipStream_t s, LevelGeom g0, float *inv_lambda) {
   const int n = g0.w * g0.h;
   hipLaunchKernelGGL(k_inv_lambda, dim3((n + 255) / 256), dim3(256), 0, s, g0, inv_lambda);
+}
+
+// ---------------------------------------------------------------------------
+// Multi-start ICP: k_icp_acc's iteration for a batch of poses.
+// (Behind every other kernel of the file: their code is the parent's.)
+//
+// One launch = one iteration at one level for all n poses.  Block b takes pixel
+// block b % pb of the floor-covered region in icp_load_cur's order (pb = the
+// blocks k_icp_acc would launch) and the poses [c chunk, + chunk) of the batch,
+// c = b / pb.  Its lanes' current-frame vertices and normals are loaded once
+// and stay in registers over the chunk.  Per pose: a failed pose is stepped over
+// by the whole block (the flag is read before the block's ticket for that pose,
+// and only the holder of the pose's last ticket writes it, so every thread of
+// every block reads the same value); otherwise icp_lane, icp_block_reduce, 27
+// device-scope int64 adds into the pose's own row, the wait for them, and the
+// pose's ticket.  The block that draws ticket pb - 1 reads and clears the row
+// and the ticket and runs icp_update on wave 0: the new pose and x, or the fail
+// flag and the stop point (level, iter).  Sums are exact and order-free as in
+// k_icp_acc, so the result does not depend on chunk or on the block order.
+// The pose is read with a uniform address and moved to scalar registers.
+__device__ __forceinline__ float uniform_f(float v) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+#ifndef KFX_ICP_MULTI_MINB
+#define KFX_ICP_MULTI_MINB 1  // multi-start ICP: blocks per CU the register budget is sized for (184 VGPRs, no scratch, 2 waves per SIMD = the 512-block grid resident; 3 spills 52 bytes per lane, 4 spills 236)
+#endif
+__global__ __launch_bounds__(kIcpThreads, KFX_ICP_MULTI_MINB) void k_icp_multi(LevelGeom g, int xe, int npix,
+                                                           const float *__restrict__ cv,
+                                                           const float *__restrict__ cn,
+                                                           const float *__restrict__ pv,
+                                                           const float *__restrict__ pn, float dist2_max,
+                                                           float sine2_max, IcpMultiPose *poses, int n, int chunk,
+                                                           int pb, unsigned long long *__restrict__ rows,
+                                                           unsigned *__restrict__ tickets, int level, int iter) {
+  f3 n0[kIcpPix], v0[kIcpPix];
+  bool ok[kIcpPix];
+  icp_load_cur(g, xe, npix, blockIdx.x % pb, kIcpPix, cv, cn, n0, v0, ok);
+  __shared__ IcpRed red;
+  __shared__ int last;
+  __shared__ double sumd[27];
+  const int k0 = (blockIdx.x / pb) * chunk, k1 = min(n, k0 + chunk);
+  for (int k = k0; k < k1; ++k) {
+    IcpMultiPose *mp = poses + k;
+    if (__builtin_amdgcn_readfirstlane(mp->fail)) continue;  // block-uniform: its barriers are skipped together
+    DevPose P;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) P.R[i] = uniform_f(mp->pose.R[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) P.t[i] = uniform_f(mp->pose.t[i]);
+    double acc[27];
+    icp_lane(g, P, n0, v0, ok, kIcpPix, pv, pn, dist2_max, sine2_max, acc);
+    const long long bsum = icp_block_reduce(red, acc);
+    unsigned long long *row = rows + (size_t)k * 27;
+    if (threadIdx.x < 64) {
+      if (threadIdx.x < 27)
+        __hip_atomic_fetch_add(&row[threadIdx.x], (unsigned long long)bsum, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (threadIdx.x == 0) {
+        const unsigned t = __hip_atomic_fetch_add(&tickets[k], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = (t == (unsigned)pb - 1u);
+      }
+    }
+    __syncthreads();
+    if (!last) continue;  // block-uniform
+    if (threadIdx.x < 27)
+      sumd[threadIdx.x] = icp_sum_value((long long)__hip_atomic_exchange(&row[threadIdx.x], 0ull, __ATOMIC_RELAXED,
+                                                                         __HIP_MEMORY_SCOPE_AGENT));
+    if (threadIdx.x == 0) __hip_atomic_store(&tickets[k], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (threadIdx.x < 64) {  // wave 0 solves
+      DevPose p = P;
+      double x[6];
+      const int f = icp_update(sumd, p, x);
+      if (threadIdx.x == 0) {
+        if (f) {
+          mp->fail = 1;
+          mp->stop_level = level;
+          mp->stop_iter = iter;
+        } else {
+          mp->pose = p;
+          mp->solves += 1;
+#pragma unroll
+          for (int i = 0; i < 6; ++i) mp->x[i] = x[i];
+        }
+      }
+    }
+  }
+}
+
+static_assert(kIcpMultiBlockPix == kIcpBlockPix, "the chunk rule counts this file's pixel blocks");
+int icp_multi_chunk(int w, int h, long long n) { return icp_multi_chunk_rule(w, h, n); }
+
+void launch_icp_multi(hipStream_t s, const LevelGeom &g, const float *cv, const float *cn, const float *pv,
+                      const float *pn, float dist_thr, float angle_thr, IcpMultiPose *poses, int n,
+                      unsigned long long *rows, unsigned *tickets, int level, int iter) {
+  int xe;
+  const int npix = icp_npix(g, &xe);
+  const int pb = icp_blocks(g);
+  const int chunk = icp_multi_chunk(g.w, g.h, n);
+  hipLaunchKernelGGL(k_icp_multi, dim3(pb * ((n + chunk - 1) / chunk)), dim3(kIcpThreads), 0, s, g, xe, npix, cv, cn,
+                     pv, pn, sqrt_le_bound(dist_thr), sqrt_le_bound(angle_thr), poses, n, chunk, pb, rows, tickets,
+                     level, iter);
 }
 
 }  // namespace kfx

@@ -23,13 +23,21 @@
 // where the window has moved on; a thirteenth names a text file that gets one
 // line per processed frame, DESIGN.md §26: frame index, kfx_pipeline's status,
 // the six label counts at level 0, fitness and rmse of kfx_frame_quality after
-// the frame).  An empty name skips its output, the followed cloud's included,
-// so that a later argument can be given alone.
+// the frame; a fourteenth is a number N > 0, DESIGN.md §27: after every Nth
+// frame, frame N on, the frame is tracked again against the model seen from the
+// pose N frames back, kfx_track_view from the identity start, and one line goes
+// to the standard output: "track_view", the frame index, the status, the
+// distance (m) and the angle (rad) between the world pose recovered and the one
+// the tracker recorded, fitness and rmse at the pose reached; status -1 and
+// zeros where the record does not reach N frames back).  An empty name skips its
+// output, the followed cloud's included, so that a later argument can be given alone.
 //   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
 //                  [followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply]
-//                  [world_view.ppm] [quality.txt]
+//                  [world_view.ppm] [quality.txt] [N]
 #include <chrono>
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 #include "../../include/kfx.h"
@@ -39,7 +47,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr,
                  "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm] "
                  "[followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply] "
-                 "[world_view.ppm] [quality.txt]\n",
+                 "[world_view.ppm] [quality.txt] [N]\n",
                  argv[0]);
     return 2;
   }
@@ -85,6 +93,8 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "error: cannot open %s\n", argv[13]);
     return 1;
   }
+  const int every = argc > 14 && argv[14][0] ? std::atoi(argv[14]) : 0;  // track against an earlier view
+  std::vector<kfx_pose> record;
   for (int k = 0; k < n; ++k) {
     if (kfx_dataset_read(ds, k, bgr.data(), depth.data()) != KFX_OK) {
       std::printf("no image! (%s)\n", kfx_last_error());
@@ -108,6 +118,39 @@ int main(int argc, char **argv) {
       }
       std::fprintf(qlog, "%d %d %lld %lld %lld %lld %lld %lld %.9g %.9g\n", k, r, (long long)q.n[0], (long long)q.n[1],
                    (long long)q.n[2], (long long)q.n[3], (long long)q.n[4], (long long)q.n[5], fitness, rmse);
+    }
+    if (every > 0 && k > 0 && k % every == 0) {
+      int got = 0;
+      if (kfx_get_pose_record(ctx, nullptr, 0, &got) != KFX_OK) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      record.resize((size_t)got);
+      if (got > 0 && kfx_get_pose_record(ctx, record.data(), got, &got) != KFX_OK) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      int status = -1;
+      double dist = 0, angle = 0, fitness = 0, rmse = 0;
+      if (got - 1 - every >= 0) {
+        const kfx_pose id = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}};
+        const kfx_pose &tracked = record[(size_t)got - 1];
+        kfx_icp_result res;
+        kfx_icp_quality q;
+        kfx_pose world;
+        if (kfx_track_view(ctx, &record[(size_t)(got - 1 - every)], &id, 1, &res, &world, &q) != KFX_OK ||
+            kfx_quality_figures(&q, &fitness, &rmse) != KFX_OK) {
+          std::fprintf(stderr, "error: %s\n", kfx_last_error());
+          return 1;
+        }
+        status = res.status;
+        double d2 = 0, tr = 0;  // |t_w - t_t| and the angle of R_w^T R_t from its trace
+        for (int i = 0; i < 3; ++i) d2 += ((double)world.t[i] - tracked.t[i]) * ((double)world.t[i] - tracked.t[i]);
+        for (int i = 0; i < 9; ++i) tr += (double)world.R[i] * tracked.R[i];
+        dist = std::sqrt(d2);
+        angle = std::acos(std::fmin(1.0, std::fmax(-1.0, (tr - 1.0) / 2.0)));
+      }
+      std::printf("track_view %d %d %.9g %.9g %.9g %.9g\n", k, status, dist, angle, fitness, rmse);
     }
     if (!follow) continue;
     if (r == KFX_TRACKING_LOST) {  // the device reset cannot move the volume back: kfx.h (the store is kept)

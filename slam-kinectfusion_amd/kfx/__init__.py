@@ -15,12 +15,12 @@ import subprocess
 
 import numpy as np
 
-from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, IcpQuality, Intrinsics, Params, Pose,
+from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, IcpQuality, IcpResult, Intrinsics, Params, Pose,
                   default_params, fptr, i16ptr, i64ptr, u8ptr, u16ptr)
 
 __all__ = ["KinectFusion", "KfxError", "Dataset", "png_info", "png_read_bgr8", "png_read_depth", "parse_intr",
            "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "write_ply_attr", "write_ply_mesh_attr",
-           "write_ply_mesh_indexed", "write_ppm", "shift_for_pose", "quality_figures", "quality_chunk", "IcpQuality", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
+           "write_ply_mesh_indexed", "write_ppm", "shift_for_pose", "quality_figures", "quality_chunk", "icp_multi_chunk", "IcpQuality", "IcpResult", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
            "default_params", "KFX_FRAME_CUR", "KFX_FRAME_PREV", "KFX_OK", "KFX_TRACKING_LOST", "EXPORTS"]
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,6 +54,7 @@ EXPORTS = [
     "kfx_debug_get_icp_step",
     "kfx_stage_icp_residuals", "kfx_score_poses", "kfx_frame_quality", "kfx_score_view", "kfx_get_quality_ms",
     "kfx_quality_figures", "kfx_quality_chunk",
+    "kfx_icp_multi", "kfx_track_view", "kfx_resume_at", "kfx_icp_multi_chunk", "kfx_get_icp_multi_ms",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
 ]
@@ -210,6 +211,11 @@ def lib():
         "kfx_get_quality_ms": ([vp, P(f)], i),
         "kfx_quality_figures": ([P(IcpQuality), P(C.c_double), P(C.c_double)], i),
         "kfx_quality_chunk": ([i, i, C.c_int64], i),
+        "kfx_icp_multi": ([vp, P(Pose), C.c_int64, P(IcpResult), P(IcpQuality)], i),
+        "kfx_track_view": ([vp, P(Pose), P(Pose), C.c_int64, P(IcpResult), P(Pose), P(IcpQuality)], i),
+        "kfx_resume_at": ([vp, P(Pose)], i),
+        "kfx_icp_multi_chunk": ([i, i, C.c_int64], i),
+        "kfx_get_icp_multi_ms": ([vp, P(f)], i),
         "kfx_dataset_open": ([C.c_char_p, P(vp)], i),
         "kfx_dataset_info": ([vp, P(Intrinsics), P(i), P(i)], i),
         "kfx_dataset_read": ([vp, i, P(C.c_uint8), P(f)], i),
@@ -287,6 +293,12 @@ def quality_figures(q: IcpQuality) -> tuple:
 def quality_chunk(width: int, height: int, n: int) -> int:
     """kfx_quality_chunk: poses one block of a score_poses batch of n walks at a width x height level."""
     return _check(lib().kfx_quality_chunk(int(width), int(height), int(n)), "kfx_quality_chunk",
+                  ok=range(1, 17))
+
+
+def icp_multi_chunk(width: int, height: int, n: int) -> int:
+    """kfx_icp_multi_chunk: poses one block of an icp_multi batch of n walks at a width x height level."""
+    return _check(lib().kfx_icp_multi_chunk(int(width), int(height), int(n)), "kfx_icp_multi_chunk",
                   ok=range(1, 17))
 
 
@@ -861,6 +873,44 @@ class KinectFusion:
         a = (C.c_float * 2)()
         _check(lib().kfx_get_quality_ms(self._h, a), "kfx_get_quality_ms")
         return {"residuals": float(a[0]), "view": float(a[1])}
+
+    # ---- multi-start ICP, tracking against a view, resuming --
+    def icp_multi(self, starts, quality: bool = False):
+        """kfx_icp_multi: the coarse-to-fine ICP loop of CUR against PREV from every start (Pose or 4x4) in
+        one batch.  Returns one IcpResult per start, or with quality=True (results, records): the level-0
+        IcpQuality of each pose reached."""
+        ps = [p if isinstance(p, Pose) else Pose.from_matrix(p) for p in starts]
+        arr = (Pose * max(len(ps), 1))(*ps)
+        out = (IcpResult * max(len(ps), 1))()
+        q = (IcpQuality * max(len(ps), 1))() if quality else None
+        _check(lib().kfx_icp_multi(self._h, arr, len(ps), out, q), "kfx_icp_multi")
+        res = list(out)[:len(ps)]
+        return (res, list(q)[:len(ps)]) if quality else res
+
+    def track_view(self, cam_pose, starts, quality: bool = False):
+        """kfx_track_view: the same loop against the volume seen from the world pose cam_pose.  Returns
+        (results, world) with world[k] = cam_pose * results[k].pose as Pose, and the records behind them
+        with quality=True."""
+        V = cam_pose if isinstance(cam_pose, Pose) else Pose.from_matrix(cam_pose)
+        ps = [p if isinstance(p, Pose) else Pose.from_matrix(p) for p in starts]
+        arr = (Pose * max(len(ps), 1))(*ps)
+        out = (IcpResult * max(len(ps), 1))()
+        world = (Pose * max(len(ps), 1))()
+        q = (IcpQuality * max(len(ps), 1))() if quality else None
+        _check(lib().kfx_track_view(self._h, C.byref(V), arr, len(ps), out, world, q), "kfx_track_view")
+        res, wl = list(out)[:len(ps)], list(world)[:len(ps)]
+        return (res, wl, list(q)[:len(ps)]) if quality else (res, wl)
+
+    def resume_at(self, cam_pose):
+        """kfx_resume_at: the next frame tracks from the world pose cam_pose against the volume as it stands."""
+        V = cam_pose if isinstance(cam_pose, Pose) else Pose.from_matrix(cam_pose)
+        _check(lib().kfx_resume_at(self._h, C.byref(V)), "kfx_resume_at")
+
+    def icp_multi_ms(self) -> dict:
+        """Device ms of the last icp_multi / track_view: the view raycasts, the loop, the final scoring (0: none)."""
+        a = (C.c_float * 3)()
+        _check(lib().kfx_get_icp_multi_ms(self._h, a), "kfx_get_icp_multi_ms")
+        return {"view": float(a[0]), "loop": float(a[1]), "score": float(a[2])}
 
     # ---- moving volume (DESIGN.md §20) ------------------------------------
     def shift_volume(self, shift):

@@ -75,6 +75,18 @@ class IcpQuality(C.Structure):
         return tuple(self.n[:]) + (int(self.sum_r2), float(self.max_abs_r), int(self.level))
 
 
+class IcpResult(C.Structure):
+    """kfx_icp_result (112 bytes): the relative pose a start reached, the status, the failing solve's
+    (level, iteration) or (-1, -1), the solves that succeeded and the last one's increment."""
+    _fields_ = [("pose", Pose), ("status", C.c_int32), ("stop_level", C.c_int32), ("stop_iter", C.c_int32),
+                ("solves", C.c_int32), ("x", C.c_double * 6)]
+
+    def fields(self) -> tuple:
+        """Everything as integers and bit patterns: what an exact comparison compares."""
+        return (bytes(self.pose), int(self.status), int(self.stop_level), int(self.stop_iter), int(self.solves),
+                bytes(self.x))
+
+
 def default_params(dims: int = 512, range_m: float = 3.0) -> Params:
     """kinectfuison_params::default_params (kinectfusion.cpp:167-190), with the
     volume size/range overridable (BASELINE configs use 4 mm / 2 mm voxels)."""
