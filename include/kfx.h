@@ -1063,6 +1063,167 @@ int kfx_resume_at(kfx_ctx *ctx, const kfx_pose *cam_pose);
 int kfx_icp_multi_chunk(int width, int height, int64_t n);
 int kfx_get_icp_multi_ms(kfx_ctx *ctx, float out_ms[3]);
 
+/* ---- relocalisation: fern keyframes, batched search, map kept on loss
+ * Added under ABI version 2, nothing else changed.  The source of pose
+ * hypotheses §26 / §27 left to the caller: a device-resident keyframe store
+ * with randomized-fern frame codes (Glocker et al., "Real-Time RGB-D Camera
+ * Relocalization via Randomized Ferns for Keyframe Encoding"), a batched
+ * nearest-keyframe search, and the per-frame call that uses both without ever
+ * dropping the map.  Off the frame path: no frame kernel or graph changes.
+ *
+ * Fern grid: the coarsest pyramid level L-1, wL x hL pixels, s = 2^(L-1).
+ * Fern: kfx_fern, 0 <= x < wL, 0 <= y < hL, td in metres.
+ * Table: m ferns, m a multiple of 16 in 16..1024, supplied by the caller or
+ * generated from (seed, depth_min_mm, depth_max_mm) with splitmix64
+ *   state += 0x9E3779B97F4A7C15; z = state;
+ *   z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB;
+ *   next = z ^ z>>31
+ * per fern in this order: x = next % wL, y = next % hL, tb, tg, tr each
+ * next % 256, td = (float)(depth_min_mm + next % (depth_max_mm - depth_min_mm
+ * + 1)) / 1000.0f (one float32 division).  Defaults (a NULL kfx_fern_params):
+ * m = 512, seed = 2013, depth 400..4000 mm.
+ * Code of a frame: the frame is the CUR maps as they stand and the BGR image
+ * they were made from (the one last given with kfx_pipeline* or
+ * kfx_stage_preprocess: what the integrate stage would fuse).  Fern f yields a
+ * nibble: bit 0 is SumB > tb * s*s, SumB the integer sum of the B bytes over the
+ * s x s block of full-resolution pixels [x*s, x*s+s) x [y*s, y*s+s); bits 1
+ * and 2 the same for G and R; bit 3 is d > td, d the CUR dmap of level L-1 at
+ * (x, y) in metres (kfx_get_frame_maps; a hole, d = 0, gives 0).  Every compare
+ * is strict and the arithmetic integer or one float compare: the code is exact.
+ * Packed: m/16 uint64_t words, fern f in word f/16, bits 4*(f%16) .. +3.
+ * Distance of two codes: the ferns whose nibbles differ, 0..m.
+ * Match order: ascending (distance, keyframe id); the key is unique, so every
+ * result is deterministic whatever the grid.
+ * Keyframe: an id (0, 1, 2, ... in order of insertion, never reused), a world
+ * camera pose and a code.
+ *
+ * kfx_fern_table (host only): the generated table for a camera and pyramid
+ * height.  kfx_keyframes_create: an empty store on ctx's device (table NULL:
+ * generated; params NULL: the defaults; with a table only n_ferns is used).
+ * kfx_encode_frame: the frame's code (m/16 words).  kfx_keyframes_add: encode
+ * and store at cam_pose (NULL: kfx_get_cur_camera_pose).  kfx_keyframes_put: a
+ * pose and a code made elsewhere (host only; uploaded by the next call that
+ * needs it).  kfx_keyframes_consider: encode, find the nearest keyframe, add
+ * the frame at the current pose iff the store is empty or that distance is
+ * > min_distance; *id the new id or -1, *nearest (may be NULL) the nearest
+ * before the add ({-1, -1}: the store was empty).  kfx_keyframes_get: either
+ * output may be NULL.  kfx_keyframes_search: the k nearest keyframes of each of
+ * q codes (NULL: the frame's own code, q = 1) in match order, q*k entries;
+ * slots past the store's size are {-1, -1}.  q in 0..65536 (0: nothing done,
+ * KFX_OK), k in 1..16.  One launch per batch plus a small merge: a block keeps
+ * 256 keyframes' words in registers and walks kfx_keyframes_search_chunk(n, q)
+ * queries (host only: with kb = ceil(n / 256) keyframe blocks,
+ * clamp(q / ceil(512 / kb), 1, 16)); results do not depend on it.
+ * kfx_keyframes_export / _import: the store as plain data (a magic word, a
+ * version, the parameters, grid, table, poses, codes).  blob NULL or cap too
+ * small: *bytes alone is written (KFX_OK when blob is NULL, else KFX_ERR_ARG).
+ * A blob that is truncated, corrupted or whose m or grid disagrees with the
+ * importing context: KFX_ERR_ARG.  kfx_get_keyframe_ms: device ms (HIP events)
+ * of the last encode [0] and the last search [1].
+ *
+ * The calls that take a context behave as kfx_score_poses: on the frame stream
+ * behind every queued frame, blocking, writing only buffers of their own
+ * (grown on demand, freed in kfx_destroy or kfx_keyframes_destroy), outside
+ * every captured graph; DevState is not written and a pending tracking status
+ * is left to the next kfx_synchronize.  A store is tied to the device and the
+ * fern grid of the context it was created with (another context: KFX_ERR_ARG)
+ * and may outlive it only for the host-only calls.  Argument errors write
+ * nothing.
+ *
+ * kfx_relocalise, on the CUR maps as they stand: encode the frame, search the k
+ * nearest keyframes, and for each match in match order run
+ * kfx_track_view(keyframe pose, starts, n, ..., q) (starts NULL: the identity,
+ * n = 1).  The candidates are the (match, start) pairs whose status is KFX_OK.
+ * The winner has the largest fitness n[0] / (n[0]+n[2]+n[3]+n[4]), compared
+ * exactly by integer cross-multiplication (a zero denominator loses); a tie
+ * goes to the smaller sum_r2 / n[0] by a 128-bit cross product, then to the
+ * earlier match, then the earlier start.  It is accepted iff
+ * kfx_quality_figures' fitness >= min_fitness: status KFX_OK, the return value
+ * too; else status and return value KFX_TRACKING_LOST, keyframe, distance and
+ * start -1 and world, icp, q zero.  n_matches: keyframes retrieved;
+ * n_converged: candidates.  Writes no tracker state: the caller adopts the pose
+ * with kfx_resume_at.  KFX_ERR_STATE on one slab of several.
+ *
+ * kfx_pipeline_recover: "probe, then commit", composed on the host from the
+ * calls above, so a committed frame is a kfx_pipeline frame.  Frame count 1:
+ * kfx_pipeline, event 1.  Otherwise probe with kfx_stage_preprocess and
+ * kfx_stage_icp (DevState restored, nothing reset).  Probe KFX_OK:
+ * kfx_pipeline, event 0.  Probe lost: kfx_relocalise(k, identity,
+ * min_fitness); a candidate accepted: kfx_resume_at(world) and probe again;
+ * that probe KFX_OK: kfx_pipeline, event 2; lost: event 3, return
+ * KFX_TRACKING_LOST, the volume untouched (the pose kfx_resume_at appended
+ * stays in the pose record, and PREV is the model seen from it).  No candidate:
+ * event 3, KFX_TRACKING_LOST, nothing written but the CUR maps.  After event
+ * 0, 1 or 2, if kfx_frame_quality's level-0 fitness >= harvest_min_fitness (the
+ * bootstrap frame always passes): kfx_keyframes_consider(harvest_min_distance),
+ * keyframe_added = the new id or -1.  report->reloc is kfx_relocalise's result
+ * where it ran, else status KFX_OK with -1 / zero fields.  params NULL: k = 4,
+ * harvest_min_distance = m / 10, min_fitness = 0.15, harvest_min_fitness = 0.25
+ * (a frame at its tracked pose reads 0.28..0.50 on the synthetic sequences, one
+ * turned 5 degrees away 0.08: DESIGN.md §26, §28).
+ * The price over kfx_pipeline is one extra preprocess and kfx_stage_icp per
+ * frame, with their host syncs.  KFX_ERR_STATE on one slab of
+ * several.  Holds in graph mode 0 and 1, with frame overlap on or off. */
+typedef struct kfx_fern {
+  int32_t x, y;
+  uint8_t tb, tg, tr, pad;
+  float td;
+} kfx_fern; /* 16 bytes */
+typedef struct kfx_keyframes kfx_keyframes; /* device-resident, tied to ctx's device */
+typedef struct kfx_fern_params {
+  int32_t n_ferns;
+  uint32_t depth_min_mm, depth_max_mm;
+  uint64_t seed;
+} kfx_fern_params;
+typedef struct kfx_keyframe_match {
+  int32_t id;
+  int32_t distance;
+} kfx_keyframe_match;
+typedef struct kfx_reloc_result {
+  int32_t status;                    /* KFX_OK: a candidate was accepted; KFX_TRACKING_LOST: none */
+  int32_t keyframe, distance, start; /* the winning candidate (-1 when none) */
+  int32_t n_matches, n_converged;
+  kfx_pose world;                    /* camera world pose of the winner */
+  kfx_icp_result icp;
+  kfx_icp_quality q;
+} kfx_reloc_result; /* 248 bytes */
+typedef struct kfx_recover_params {
+  int32_t k;
+  int32_t harvest_min_distance;
+  double min_fitness, harvest_min_fitness;
+} kfx_recover_params;
+typedef struct kfx_recover_report {
+  int32_t event; /* 0 tracked, 1 bootstrap, 2 relocalised, 3 lost, map kept */
+  int32_t keyframe_added;
+  kfx_reloc_result reloc;
+} kfx_recover_report;
+#ifdef __cplusplus
+static_assert(sizeof(kfx_fern) == 16 && sizeof(kfx_reloc_result) == 248, "kfx_fern is 16 bytes, kfx_reloc_result 248");
+#else
+_Static_assert(sizeof(kfx_fern) == 16 && sizeof(kfx_reloc_result) == 248, "kfx_fern is 16 bytes, kfx_reloc_result 248");
+#endif
+int kfx_fern_table(const kfx_intrinsics *intr, int pyramid_height, const kfx_fern_params *params, kfx_fern *out);
+int kfx_keyframes_create(kfx_ctx *ctx, const kfx_fern_params *params, const kfx_fern *table, kfx_keyframes **out);
+int kfx_keyframes_destroy(kfx_keyframes *kf);
+int kfx_keyframes_get_table(const kfx_keyframes *kf, kfx_fern *out);
+int kfx_keyframes_count(const kfx_keyframes *kf, int64_t *n);
+int kfx_encode_frame(kfx_ctx *ctx, kfx_keyframes *kf, uint64_t *code);
+int kfx_keyframes_add(kfx_ctx *ctx, kfx_keyframes *kf, const kfx_pose *cam_pose, int32_t *id);
+int kfx_keyframes_put(kfx_keyframes *kf, const kfx_pose *cam_pose, const uint64_t *code, int32_t *id);
+int kfx_keyframes_consider(kfx_ctx *ctx, kfx_keyframes *kf, int32_t min_distance, int32_t *id,
+                           kfx_keyframe_match *nearest);
+int kfx_keyframes_get(const kfx_keyframes *kf, int32_t id, kfx_pose *cam_pose, uint64_t *code);
+int kfx_keyframes_search(kfx_ctx *ctx, kfx_keyframes *kf, const uint64_t *codes, int64_t q, int k,
+                         kfx_keyframe_match *out);
+int kfx_keyframes_search_chunk(int64_t n_keyframes, int64_t q);
+int kfx_keyframes_export(const kfx_keyframes *kf, void *blob, int64_t cap, int64_t *bytes);
+int kfx_keyframes_import(kfx_ctx *ctx, const void *blob, int64_t bytes, kfx_keyframes **out);
+int kfx_get_keyframe_ms(kfx_ctx *ctx, float out_ms[2]);
+int kfx_relocalise(kfx_ctx *ctx, kfx_keyframes *kf, int k, const kfx_pose *starts, int64_t n, double min_fitness,
+                   kfx_reloc_result *out);
+int kfx_pipeline_recover(kfx_ctx *ctx, kfx_keyframes *kf, const uint8_t *bgr, const float *depth_mm,
+                         const kfx_recover_params *params, kfx_recover_report *report);
+
 #ifdef __cplusplus
 }
 #endif

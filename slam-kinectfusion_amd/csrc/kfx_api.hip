@@ -1155,6 +1155,10 @@ int kfx_destroy(kfx_ctx *c) {
     if (b) (void)hipFree(b);
   for (hipEvent_t e : c->ev_m)
     if (e) (void)hipEventDestroy(e);
+  for (void *b : c->kf_buf)
+    if (b) (void)hipFree(b);
+  for (hipEvent_t e : c->ev_kf)
+    if (e) (void)hipEventDestroy(e);
   if (c->world_tris) (void)hipFree(c->world_tris);
   for (void *b : c->wv_buf)
     if (b) (void)hipFree(b);

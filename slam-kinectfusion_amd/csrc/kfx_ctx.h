@@ -215,6 +215,13 @@ struct kfx_ctx {
   size_t m_cap[3]{};
   hipEvent_t ev_m[4]{};
   float m_ms[3]{};
+  // fern keyframes.  Buffers of its own (grown on demand, kept,
+  // freed in kfx_destroy): [0] a search's queries, [1] its per-block keys, [2]
+  // its results.  Events: the last encode [0, 1], the last search [2, 3].
+  void *kf_buf[3]{};
+  size_t kf_cap[3]{};
+  hipEvent_t ev_kf[4]{};
+  float kf_ms[2]{};
   uint8_t *mc_tab = nullptr;    // marching-cubes table (uploaded on first use)
   // per pixel: [key | pend | Ts | nx | ny | nz] planes (k_raycast<kSlab>): the
   // sample index of this slab's decisive event, the first sample a bounded

@@ -1,8 +1,9 @@
 // kfx_export.hip — the host side of what reads the model out: the
 // free-viewpoint render, point cloud / mesh extraction and PLY files, the
 // moving volume, bricks out and back in, the world map, the indexed mesh and the world view
-// (DESIGN.md §18, §20-§25).  Host code only (no __global__ function: the kernels are in
-// kfx_extract / kfx_view / kfx_shift / kfx_world / kfx_world_view.hip); no frame runs any of it.
+// (DESIGN.md §18, §20-§25), and of what scores, tracks and relocalises off the frame path (§26-§28).
+// Host code only (no __global__ function: the kernels are in kfx_extract / kfx_view / kfx_shift /
+// kfx_world / kfx_world_view / kfx_quality / kfx_reloc.hip); no frame runs any of it.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -13,7 +14,21 @@
 
 #include "kfx_ctx.h"
 #include "kfx_multi.h"
+#include "kfx_reloc.h"
 #include "kfx_scanws.h"
+
+// The keyframe store: the host mirror (table, poses, codes) and
+// on `device` the table, the word-major code table (word w of keyframe i at
+// d_codes[w * cap + i]; keyframes [0, synced) are uploaded, the rest wait for
+// the next call that searches) and the m / 16 words of the last encode.
+struct kfx_keyframes {
+  KeyframeHost h;
+  int device = 0;
+  int width = 0, height = 0;  // the camera whose frames it encodes
+  kfx_fern *d_table = nullptr;
+  unsigned long long *d_codes = nullptr, *d_code = nullptr;
+  int64_t cap = 0, synced = 0;
+};
 
 namespace {
 
@@ -1558,6 +1573,489 @@ int kfx_resume_at(kfx_ctx *c, const kfx_pose *cam_pose) {
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) Rinv[3 * i + j] = c2v.R[3 * j + i];
   return kfx_stage_raycast(c, &cam2vol, Rinv);
+}
+
+// ---- fern keyframes and relocalisation -----------------------
+
+static const kfx_fern_params kFernDefaults = {512, 400u, 4000u, 2013ull};
+constexpr int64_t kMaxKeyframes = (int64_t)1 << 24;
+constexpr size_t kSearchPartBytes = (size_t)64 << 20;  // the per-block keys of one search launch at the most
+
+static bool pose_finite(const kfx_pose &p) {
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? p.R[i] : p.t[i - 9])) return false;
+  return true;
+}
+
+int kfx_fern_table(const kfx_intrinsics *intr, int pyramid_height, const kfx_fern_params *params, kfx_fern *out) {
+  if (!intr || !out) return set_err(KFX_ERR_ARG, "null argument");
+  if (pyramid_height < 1 || pyramid_height > KFX_MAX_LEVELS) return set_err(KFX_ERR_ARG, "pyramid height outside 1..4");
+  const FernGrid g = fern_grid(intr->width, intr->height, pyramid_height);
+  if (intr->width < 1 || intr->height < 1 || g.wL < 1 || g.hL < 1) return set_err(KFX_ERR_ARG, "empty fern grid");
+  const kfx_fern_params p = params ? *params : kFernDefaults;
+  if (!fern_params_ok(p)) return set_err(KFX_ERR_ARG, "n_ferns: a multiple of 16 in 16..1024; depth_min_mm <= depth_max_mm");
+  fern_table(g, p, out);
+  return KFX_OK;
+}
+
+static void kf_free(kfx_keyframes *kf) {
+  (void)hipSetDevice(kf->device);
+  if (kf->d_table) (void)hipFree(kf->d_table);
+  if (kf->d_codes) (void)hipFree(kf->d_codes);
+  if (kf->d_code) (void)hipFree(kf->d_code);
+  delete kf;
+  (void)hipGetLastError();
+}
+
+// a store around the host mirror h on c's device: the table uploaded, no codes yet
+static int kf_make(kfx_ctx *c, KeyframeHost &&h, kfx_keyframes **out) {
+  kfx_keyframes *kf = new (std::nothrow) kfx_keyframes;
+  if (!kf) return set_err(KFX_ERR_OOM, "keyframes: out of memory");
+  kf->h = std::move(h);
+  kf->device = c->device;
+  kf->width = c->intr.width;
+  kf->height = c->intr.height;
+  const size_t tb = kf->h.table.size() * sizeof(kfx_fern);
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&kf->d_table), tb);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&kf->d_code), sizeof(uint64_t) * kf->h.words);
+  if (e == hipSuccess) e = hipMemcpy(kf->d_table, kf->h.table.data(), tb, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    kf_free(kf);
+    return hip_err("keyframes", e);
+  }
+  *out = kf;
+  return KFX_OK;
+}
+
+// the store belongs to this context's device and fern grid
+static int kf_args(kfx_ctx *c, const kfx_keyframes *kf) {
+  if (!kf) return set_err(KFX_ERR_ARG, "null keyframe store");
+  const FernGrid g = fern_grid(c->intr.width, c->intr.height, c->L);
+  if (kf->device != c->device || kf->width != c->intr.width || kf->height != c->intr.height || kf->h.grid.wL != g.wL ||
+      kf->h.grid.hL != g.hL || kf->h.grid.s != g.s)
+    return set_err(KFX_ERR_ARG, "the keyframe store belongs to another device or fern grid");
+  return KFX_OK;
+}
+
+int kfx_keyframes_create(kfx_ctx *c, const kfx_fern_params *params, const kfx_fern *table, kfx_keyframes **out) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out) return set_err(KFX_ERR_ARG, "null out");
+  const kfx_fern_params p = params ? *params : kFernDefaults;
+  if (!(table ? fern_count_ok(p.n_ferns) : fern_params_ok(p)))
+    return set_err(KFX_ERR_ARG, "n_ferns: a multiple of 16 in 16..1024; depth_min_mm <= depth_max_mm");
+  KeyframeHost h;
+  h.par = p;
+  h.grid = fern_grid(c->intr.width, c->intr.height, c->L);
+  h.words = p.n_ferns / 16;
+  try {
+    h.table.resize((size_t)p.n_ferns);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "keyframes: out of memory");
+  }
+  if (table) {
+    if (!fern_table_ok(h.grid, table, p.n_ferns)) return set_err(KFX_ERR_ARG, "a fern outside the grid or a bad td");
+    std::memcpy(h.table.data(), table, h.table.size() * sizeof(kfx_fern));
+  } else {
+    fern_table(h.grid, p, h.table.data());
+  }
+  return kf_make(c, std::move(h), out);
+}
+
+int kfx_keyframes_destroy(kfx_keyframes *kf) {
+  if (kf) kf_free(kf);
+  return KFX_OK;
+}
+
+int kfx_keyframes_get_table(const kfx_keyframes *kf, kfx_fern *out) {
+  if (!kf || !out) return set_err(KFX_ERR_ARG, "null argument");
+  std::memcpy(out, kf->h.table.data(), kf->h.table.size() * sizeof(kfx_fern));
+  return KFX_OK;
+}
+
+int kfx_keyframes_count(const kfx_keyframes *kf, int64_t *n) {
+  if (!kf || !n) return set_err(KFX_ERR_ARG, "null argument");
+  *n = kf->h.count();
+  return KFX_OK;
+}
+
+int kfx_keyframes_put(kfx_keyframes *kf, const kfx_pose *cam_pose, const uint64_t *code, int32_t *id) {
+  if (!kf || !cam_pose || !code) return set_err(KFX_ERR_ARG, "null argument");
+  if (!pose_finite(*cam_pose)) return set_err(KFX_ERR_ARG, "non-finite pose entry");
+  if (kf->h.count() >= kMaxKeyframes) return set_err(KFX_ERR_STATE, "the keyframe store is full");
+  int32_t k;
+  try {
+    k = kf->h.put(*cam_pose, code);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "keyframes: out of memory");
+  }
+  if (id) *id = k;
+  return KFX_OK;
+}
+
+int kfx_keyframes_get(const kfx_keyframes *kf, int32_t id, kfx_pose *cam_pose, uint64_t *code) {
+  if (!kf) return set_err(KFX_ERR_ARG, "null keyframe store");
+  if (id < 0 || id >= kf->h.count()) return set_err(KFX_ERR_ARG, "no such keyframe");
+  if (cam_pose) *cam_pose = kf->h.poses[(size_t)id];
+  if (code) std::memcpy(code, kf->h.codes.data() + (size_t)id * kf->h.words, sizeof(uint64_t) * kf->h.words);
+  return KFX_OK;
+}
+
+int kfx_keyframes_search_chunk(int64_t n_keyframes, int64_t q) {
+  if (n_keyframes < 0 || n_keyframes > kMaxKeyframes || q < 1 || q > 65536)
+    return set_err(KFX_ERR_ARG, "search_chunk: n in 0..2^24, q in 1..2^16");
+  return search_chunk_rule(n_keyframes, q);
+}
+
+int kfx_keyframes_export(const kfx_keyframes *kf, void *blob, int64_t cap, int64_t *bytes) {
+  if (!kf || !bytes) return set_err(KFX_ERR_ARG, "null argument");
+  const int64_t need = blob_bytes(kf->h);
+  *bytes = need;
+  if (!blob) return KFX_OK;
+  if (cap < need) return set_err(KFX_ERR_ARG, "export: the buffer is smaller than the blob");
+  blob_write(kf->h, blob);
+  return KFX_OK;
+}
+
+int kfx_keyframes_import(kfx_ctx *c, const void *blob, int64_t bytes, kfx_keyframes **out) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out) return set_err(KFX_ERR_ARG, "null out");
+  KeyframeHost h;
+  try {
+    if (const char *why = blob_read(blob, bytes, fern_grid(c->intr.width, c->intr.height, c->L), &h))
+      return set_err(KFX_ERR_ARG, std::string("import: ") + why);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "keyframes: out of memory");
+  }
+  if (h.count() > kMaxKeyframes) return set_err(KFX_ERR_ARG, "import: more keyframes than a store holds");
+  return kf_make(c, std::move(h), out);
+}
+
+// The device's code table holds keyframes [0, count) and has room for `need`:
+// grown (and filled again from the mirror) where it is too small, then the
+// keyframes kfx_keyframes_put left on the host uploaded, one strided copy.
+static int kf_sync(kfx_ctx *c, kfx_keyframes *kf, int64_t need) {
+  const int W = kf->h.words;
+  const int64_t n = kf->h.count();
+  if (need > kf->cap) {
+    const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(1024, 2 * kf->cap));
+    if (kf->d_codes) (void)hipFree(kf->d_codes);  // nothing queued reads it: every call that does ends with a sync
+    kf->d_codes = nullptr;
+    kf->cap = kf->synced = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&kf->d_codes), sizeof(uint64_t) * (size_t)W * (size_t)cap);
+    if (e != hipSuccess) {
+      kf->d_codes = nullptr;
+      (void)hipGetLastError();
+      return set_err(KFX_ERR_OOM, std::string("keyframes: hipMalloc: ") + hipGetErrorString(e));
+    }
+    kf->cap = cap;
+  }
+  if (kf->synced < n) {
+    const int64_t lo = kf->synced, cnt = n - lo;
+    std::vector<uint64_t> stage;
+    try {
+      stage.resize((size_t)cnt * W);
+    } catch (const std::bad_alloc &) {
+      return set_err(KFX_ERR_OOM, "keyframes: out of memory");
+    }
+    for (int64_t i = 0; i < cnt; ++i)
+      for (int w = 0; w < W; ++w) stage[(size_t)w * cnt + i] = kf->h.codes[(size_t)(lo + i) * W + w];
+    HIPCHK(hipMemcpy2DAsync(kf->d_codes + lo, sizeof(uint64_t) * (size_t)kf->cap, stage.data(), sizeof(uint64_t) * (size_t)cnt,
+                            sizeof(uint64_t) * (size_t)cnt, (size_t)W, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    kf->synced = n;
+  }
+  return KFX_OK;
+}
+
+// The frame's code: the CUR dmap of level L - 1 and the colour the integrate
+// stage would fuse, on the frame stream behind every queued frame.  slot: also
+// into the code table's column `count` (kf_sync(count + 1) came first), where
+// it counts once the host mirror takes the keyframe.  ev_kf[0, 1] time it.
+static int kf_encode(kfx_ctx *c, kfx_keyframes *kf, bool slot, uint64_t *code) {
+  int r;
+  if ((r = make_events(c->ev_kf, 4))) return r;
+  const int W = kf->h.words;
+  HIPCHK(hipEventRecord(c->ev_kf[0], c->stream));
+  launch_fern_encode(c->stream, kf->d_table, kf->h.par.n_ferns, c->last_bgr ? c->last_bgr : c->bgr, c->intr.width,
+                     c->cur.d[c->L - 1], kf->h.grid.wL, kf->h.grid.s, kf->d_code,
+                     slot ? kf->d_codes + kf->h.count() : nullptr, kf->cap);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_kf[1], c->stream));
+  HIPCHK(hipMemcpyAsync(code, kf->d_code, sizeof(uint64_t) * W, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->kf_ms[0], c->ev_kf[0], c->ev_kf[1]));
+  return KFX_OK;
+}
+
+// The k nearest keyframes of q codes (host; null: the last encode's, on the
+// device, q = 1), q * k matches in match order.  Launches of at most
+// kSearchPartBytes of per-block keys each.  ev_kf[2, 3] time them.
+static int kf_search(kfx_ctx *c, kfx_keyframes *kf, const uint64_t *codes, int64_t q, int k, kfx_keyframe_match *out) {
+  static_assert(sizeof(kfx_keyframe_match) == sizeof(uint64_t), "a match is a key's two halves");
+  int r;
+  const int W = kf->h.words;
+  const int64_t n = kf->h.count();
+  c->kf_ms[1] = 0.f;
+  if (n == 0) {
+    for (int64_t i = 0; i < q * k; ++i) out[i] = {-1, -1};
+    return KFX_OK;
+  }
+  if ((r = kf_sync(c, kf, n))) return r;
+  const size_t per_query = (size_t)search_key_blocks(n) * k * sizeof(uint64_t);
+  const int64_t qb = std::max<int64_t>(1, std::min<int64_t>(q, (int64_t)(kSearchPartBytes / per_query)));
+  if (codes && (r = reserve(&c->kf_buf[0], &c->kf_cap[0], sizeof(uint64_t) * (size_t)q * W, "search"))) return r;
+  if ((r = reserve(&c->kf_buf[1], &c->kf_cap[1], per_query * (size_t)qb, "search"))) return r;
+  if ((r = reserve(&c->kf_buf[2], &c->kf_cap[2], sizeof(uint64_t) * (size_t)q * k, "search"))) return r;
+  if ((r = make_events(c->ev_kf, 4))) return r;
+  if (codes)
+    HIPCHK(hipMemcpyAsync(c->kf_buf[0], codes, sizeof(uint64_t) * (size_t)q * W, hipMemcpyHostToDevice, c->stream));
+  const unsigned long long *dq = codes ? static_cast<const unsigned long long *>(c->kf_buf[0]) : kf->d_code;
+  unsigned long long *dout = static_cast<unsigned long long *>(c->kf_buf[2]);
+  HIPCHK(hipEventRecord(c->ev_kf[2], c->stream));
+  for (int64_t q0 = 0; q0 < q; q0 += qb)
+    launch_fern_search(c->stream, kf->d_codes, kf->cap, (int)n, W, dq + (size_t)q0 * W, (int)std::min(qb, q - q0), k,
+                       static_cast<unsigned long long *>(c->kf_buf[1]), dout + (size_t)q0 * k);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->ev_kf[3], c->stream));
+  HIPCHK(hipMemcpyAsync(out, dout, sizeof(uint64_t) * (size_t)q * k, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->kf_ms[1], c->ev_kf[2], c->ev_kf[3]));
+  return KFX_OK;
+}
+
+int kfx_encode_frame(kfx_ctx *c, kfx_keyframes *kf, uint64_t *code) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = kf_args(c, kf))) return r;
+  if (!code) return set_err(KFX_ERR_ARG, "null code");
+  uint64_t tmp[kFernMaxWords];
+  if ((r = kf_encode(c, kf, false, tmp))) return r;
+  std::memcpy(code, tmp, sizeof(uint64_t) * kf->h.words);
+  return KFX_OK;
+}
+
+// encode into the table's next column and take the keyframe into the mirror
+static int kf_add(kfx_ctx *c, kfx_keyframes *kf, const kfx_pose &pose, bool encoded, uint64_t *code, int32_t *id) {
+  int r;
+  if (kf->h.count() >= kMaxKeyframes) return set_err(KFX_ERR_STATE, "the keyframe store is full");
+  if (!encoded) {
+    if ((r = kf_sync(c, kf, kf->h.count() + 1))) return r;
+    if ((r = kf_encode(c, kf, true, code))) return r;
+  }
+  int32_t k;
+  try {
+    k = kf->h.put(pose, code);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "keyframes: out of memory");
+  }
+  kf->synced = kf->h.count();  // the encode wrote this column
+  if (id) *id = k;
+  return KFX_OK;
+}
+
+int kfx_keyframes_add(kfx_ctx *c, kfx_keyframes *kf, const kfx_pose *cam_pose, int32_t *id) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = kf_args(c, kf))) return r;
+  kfx_pose pose;
+  if (cam_pose) {
+    if (!pose_finite(*cam_pose)) return set_err(KFX_ERR_ARG, "non-finite pose entry");
+    pose = *cam_pose;
+  } else if ((r = kfx_get_cur_camera_pose(c, &pose))) {
+    return r;
+  }
+  uint64_t code[kFernMaxWords];
+  return kf_add(c, kf, pose, false, code, id);
+}
+
+int kfx_keyframes_consider(kfx_ctx *c, kfx_keyframes *kf, int32_t min_distance, int32_t *id,
+                           kfx_keyframe_match *nearest) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = kf_args(c, kf))) return r;
+  if (!id) return set_err(KFX_ERR_ARG, "null id");
+  if (kf->h.count() >= kMaxKeyframes) return set_err(KFX_ERR_STATE, "the keyframe store is full");
+  kfx_pose pose;
+  if ((r = kfx_get_cur_camera_pose(c, &pose))) return r;
+  uint64_t code[kFernMaxWords];
+  if ((r = kf_sync(c, kf, kf->h.count() + 1))) return r;
+  if ((r = kf_encode(c, kf, true, code))) return r;
+  kfx_keyframe_match m = {-1, -1};
+  if (kf->h.count() && (r = kf_search(c, kf, nullptr, 1, 1, &m))) return r;
+  int32_t added = -1;
+  if (m.id < 0 || m.distance > min_distance)
+    if ((r = kf_add(c, kf, pose, true, code, &added))) return r;
+  *id = added;
+  if (nearest) *nearest = m;
+  return KFX_OK;
+}
+
+int kfx_keyframes_search(kfx_ctx *c, kfx_keyframes *kf, const uint64_t *codes, int64_t q, int k,
+                         kfx_keyframe_match *out) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = kf_args(c, kf))) return r;
+  if (q < 0 || q > 65536) return set_err(KFX_ERR_ARG, "q outside 0..2^16");
+  if (k < 1 || k > kSearchMaxK) return set_err(KFX_ERR_ARG, "k outside 1..16");
+  if (q == 0) return KFX_OK;
+  if (!out) return set_err(KFX_ERR_ARG, "null out");
+  if (!codes) {
+    uint64_t code[kFernMaxWords];
+    q = 1;
+    if ((r = kf_encode(c, kf, false, code))) return r;
+  }
+  std::vector<kfx_keyframe_match> res;
+  try {
+    res.resize((size_t)q * k);
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "search: out of memory");
+  }
+  if ((r = kf_search(c, kf, codes, q, k, res.data()))) return r;
+  std::memcpy(out, res.data(), res.size() * sizeof(kfx_keyframe_match));
+  return KFX_OK;
+}
+
+int kfx_get_keyframe_ms(kfx_ctx *c, float out_ms[2]) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if (!out_ms) return set_err(KFX_ERR_ARG, "null ms");
+  out_ms[0] = c->kf_ms[0];
+  out_ms[1] = c->kf_ms[1];
+  return KFX_OK;
+}
+
+static void reloc_none(kfx_reloc_result *o, int status) {
+  std::memset(o, 0, sizeof(*o));
+  o->status = status;
+  o->keyframe = o->distance = o->start = -1;
+}
+
+int kfx_relocalise(kfx_ctx *c, kfx_keyframes *kf, int k, const kfx_pose *starts, int64_t n, double min_fitness,
+                   kfx_reloc_result *out) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = kf_args(c, kf))) return r;
+  if (k < 1 || k > kSearchMaxK) return set_err(KFX_ERR_ARG, "k outside 1..16");
+  if (!out) return set_err(KFX_ERR_ARG, "null out");
+  if (std::isnan(min_fitness)) return set_err(KFX_ERR_ARG, "min_fitness is not a number");
+  const kfx_pose id = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}};
+  if (!starts) {
+    starts = &id;
+    n = 1;
+  }
+  if (n < 0 || n > 65536) return set_err(KFX_ERR_ARG, "n outside 0..2^16");
+  for (int64_t i = 0; i < n; ++i)
+    if (!pose_finite(starts[i])) return set_err(KFX_ERR_ARG, "non-finite pose entry");
+  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "relocalise on one slab of several");
+  uint64_t code[kFernMaxWords];
+  kfx_keyframe_match match[kSearchMaxK];
+  if ((r = kf_encode(c, kf, false, code))) return r;
+  if ((r = kf_search(c, kf, nullptr, 1, k, match))) return r;
+  int n_matches = 0;
+  while (n_matches < k && match[n_matches].id >= 0) ++n_matches;
+  std::vector<kfx_icp_result> icp;
+  std::vector<kfx_pose> world;
+  std::vector<kfx_icp_quality> qual;
+  std::vector<RelocCand> cand;
+  try {
+    icp.resize((size_t)n_matches * n);
+    world.resize(icp.size());
+    qual.resize(icp.size());
+    cand.reserve(icp.size());
+  } catch (const std::bad_alloc &) {
+    return set_err(KFX_ERR_OOM, "relocalise: out of memory");
+  }
+  for (int m = 0; m < n_matches && n > 0; ++m) {
+    const size_t o = (size_t)m * n;
+    if ((r = kfx_track_view(c, &kf->h.poses[(size_t)match[m].id], starts, n, &icp[o], &world[o], &qual[o]))) return r;
+    for (int64_t s = 0; s < n; ++s)
+      if (icp[o + s].status == KFX_OK) cand.push_back(reloc_cand(qual[o + s], m, (int)s));
+  }
+  const int best = reloc_select(cand.data(), (int)cand.size());
+  double fitness = 0.0, rmse = 0.0;
+  bool accept = false;
+  size_t at = 0;
+  if (best >= 0) {
+    at = (size_t)cand[best].match * n + cand[best].start;
+    if ((r = kfx_quality_figures(&qual[at], &fitness, &rmse))) return r;
+    accept = fitness >= min_fitness;
+  }
+  if (!accept) {
+    reloc_none(out, KFX_TRACKING_LOST);
+  } else {
+    reloc_none(out, KFX_OK);
+    out->keyframe = match[cand[best].match].id;
+    out->distance = match[cand[best].match].distance;
+    out->start = cand[best].start;
+    out->world = world[at];
+    out->icp = icp[at];
+    out->q = qual[at];
+  }
+  out->n_matches = n_matches;
+  out->n_converged = (int32_t)cand.size();
+  return out->status;
+}
+
+// kfx_stage_preprocess + kfx_stage_icp: would this frame track from the state as it stands?
+static int recover_probe(kfx_ctx *c, const uint8_t *bgr, const float *depth_mm) {
+  const int r = kfx_stage_preprocess(c, bgr, depth_mm);
+  return r ? r : kfx_stage_icp(c, nullptr);
+}
+
+int kfx_pipeline_recover(kfx_ctx *c, kfx_keyframes *kf, const uint8_t *bgr, const float *depth_mm,
+                         const kfx_recover_params *params, kfx_recover_report *report) {
+  int r = check_ctx(c);
+  if (r) return r;
+  if ((r = kf_args(c, kf))) return r;
+  if (!bgr || !depth_mm) return set_err(KFX_ERR_ARG, "null image");
+  if (!report) return set_err(KFX_ERR_ARG, "null report");
+  const kfx_recover_params p = params ? *params : kfx_recover_params{4, kf->h.par.n_ferns / 10, 0.15, 0.25};
+  if (p.k < 1 || p.k > kSearchMaxK || std::isnan(p.min_fitness) || std::isnan(p.harvest_min_fitness))
+    return set_err(KFX_ERR_ARG, "recover: k outside 1..16 or a fitness that is not a number");
+  if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "pipeline_recover on one slab of several");
+  kfx_recover_report rep;
+  rep.event = 0;
+  rep.keyframe_added = -1;
+  reloc_none(&rep.reloc, KFX_OK);
+  int count = 0;
+  if ((r = kfx_get_frame_count(c, &count))) return r;
+  if (count == 1) {
+    rep.event = 1;
+  } else {
+    r = recover_probe(c, bgr, depth_mm);
+    if (r == KFX_TRACKING_LOST) {
+      r = kfx_relocalise(c, kf, p.k, nullptr, 1, p.min_fitness, &rep.reloc);
+      if (r == KFX_OK) {
+        if ((r = kfx_resume_at(c, &rep.reloc.world))) return r;
+        r = recover_probe(c, bgr, depth_mm);
+        if (r == KFX_OK) rep.event = 2;
+      }
+      if (r == KFX_TRACKING_LOST) {  // no candidate, or the adopted pose does not track: the map is kept
+        rep.event = 3;
+        *report = rep;
+        return KFX_TRACKING_LOST;
+      }
+    }
+    if (r) return r;
+  }
+  if ((r = kfx_pipeline(c, bgr, depth_mm)) < 0) return r;
+  if (r == KFX_TRACKING_LOST) {  // the committed frame disagreed with its probe: kfx_pipeline's reset has been applied
+    *report = rep;
+    return set_err(KFX_ERR_STATE, "pipeline_recover: the probe tracked and the committed frame did not");
+  }
+  bool harvest = rep.event == 1;
+  if (!harvest) {
+    kfx_icp_quality q;
+    double fitness = 0.0, rmse = 0.0;
+    if ((r = kfx_frame_quality(c, 0, nullptr, nullptr, &q))) return r;
+    if ((r = kfx_quality_figures(&q, &fitness, &rmse))) return r;
+    harvest = fitness >= p.harvest_min_fitness;
+  }
+  if (harvest && (r = kfx_keyframes_consider(c, kf, p.harvest_min_distance, &rep.keyframe_added, nullptr))) return r;
+  *report = rep;
+  return KFX_OK;
 }
 
 }  // extern "C"

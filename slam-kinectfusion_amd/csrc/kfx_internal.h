@@ -1,5 +1,5 @@
 // kfx_internal.h — types shared by the HIP kernels (kfx_kernels.hip,
-// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip, kfx_world_view.hip, kfx_quality.hip) and the host runtime (kfx_api.hip, kfx_export.hip).  Not part of the public ABI.
+// kfx_extract.hip, kfx_volume_io.hip, kfx_view.hip, kfx_shift.hip, kfx_world.hip, kfx_world_view.hip, kfx_quality.hip, kfx_reloc.hip) and the host runtime (kfx_api.hip, kfx_export.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -437,6 +437,22 @@ int quality_chunk(int w, int h, long long n);
 void launch_quality(hipStream_t s, const LevelGeom &g, const float *cv, const float *cn, const float *pv, const float *pn,
                     float dist_thr, float angle_thr, const DevPose *poses, int n, void *rec, float *residual,
                     uint8_t *label);
+
+// ---- kfx_reloc.hip --------------------------------------------------------
+// fern keyframes.  Encode: the code of the frame (bgr of
+// `width` pixels a row, dmap of the wL-wide fern grid, sc = 2^(L-1)) under the
+// m ferns of `table` (kfx_fern records), m / 16 words to `code` and, where slot
+// is not null, to slot[w * stride] as well (a keyframe's place in the word-major
+// code table).  Search: the k smallest (distance << 32 | id) keys of each of the
+// q queries (q x W words, query-major) over keyframes 0 .. n - 1 of the
+// word-major table (word w of keyframe i at codes[w * stride + i]), ascending,
+// to out[query * k + j]; slots past n hold all ones.  Both keys' halves are a
+// kfx_keyframe_match.  part: q * ceil(n / 256) * k words of workspace.  n >= 1.
+void launch_fern_encode(hipStream_t s, const void *table, int m, const uint8_t *bgr, int width, const float *dmap, int wL,
+                        int sc, unsigned long long *code, unsigned long long *slot, long long stride);
+void launch_fern_search(hipStream_t s, const unsigned long long *codes, long long stride, int n, int W,
+                        const unsigned long long *queries, int q, int k, unsigned long long *part,
+                        unsigned long long *out);
 
 // ---- kfx_shift.hip --------------------------------------------------------
 // the moving volume, whole single volumes only.  shift: voxels

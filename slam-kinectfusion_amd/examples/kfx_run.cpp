@@ -29,11 +29,18 @@
 // to the standard output: "track_view", the frame index, the status, the
 // distance (m) and the angle (rad) between the world pose recovered and the one
 // the tracker recorded, fitness and rmse at the pose reached; status -1 and
-// zeros where the record does not reach N frames back).  An empty name skips its
+// zeros where the record does not reach N frames back); a fifteenth names a text
+// file, DESIGN.md §28: the frames then go through kfx_pipeline_recover with the
+// default parameters and a keyframe store of the default table instead of
+// kfx_pipeline, and the file gets one line per frame: frame index, the event (0
+// tracked, 1 bootstrap, 2 relocalised, 3 lost with the map kept), the keyframe
+// added or -1, the keyframe relocalised against and its code distance or -1 -1,
+// and the fitness of kfx_frame_quality after the frame (0 after event 3).  An
+// empty name skips its
 // output, the followed cloud's included, so that a later argument can be given alone.
 //   usage: kfx_run <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm]
 //                  [followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply]
-//                  [world_view.ppm] [quality.txt] [N]
+//                  [world_view.ppm] [quality.txt] [N] [recover.txt]
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -47,7 +54,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr,
                  "usage: %s <dataset dir> [poses.txt] [cloud.ply] [colored_cloud.ply] [colored_mesh.ply] [view.ppm] "
                  "[followed_cloud.ply] [stream] [world_mesh.ply] [indexed_mesh.ply] [world_indexed_mesh.ply] "
-                 "[world_view.ppm] [quality.txt] [N]\n",
+                 "[world_view.ppm] [quality.txt] [N] [recover.txt]\n",
                  argv[0]);
     return 2;
   }
@@ -94,6 +101,18 @@ int main(int argc, char **argv) {
     return 1;
   }
   const int every = argc > 14 && argv[14][0] ? std::atoi(argv[14]) : 0;  // track against an earlier view
+  std::FILE *rlog = nullptr;  // probe, then commit: the map is kept when tracking is lost
+  kfx_keyframes *keyframes = nullptr;
+  if (argc > 15 && argv[15][0]) {
+    if (!(rlog = std::fopen(argv[15], "w"))) {
+      std::fprintf(stderr, "error: cannot open %s\n", argv[15]);
+      return 1;
+    }
+    if (kfx_keyframes_create(ctx, nullptr, nullptr, &keyframes) != KFX_OK) {
+      std::fprintf(stderr, "error: %s\n", kfx_last_error());
+      return 1;
+    }
+  }
   std::vector<kfx_pose> record;
   for (int k = 0; k < n; ++k) {
     if (kfx_dataset_read(ds, k, bgr.data(), depth.data()) != KFX_OK) {
@@ -101,13 +120,26 @@ int main(int argc, char **argv) {
       break;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    const int r = kfx_pipeline(ctx, bgr.data(), depth.data());
+    kfx_recover_report rep;
+    const int r = rlog ? kfx_pipeline_recover(ctx, keyframes, bgr.data(), depth.data(), nullptr, &rep)
+                       : kfx_pipeline(ctx, bgr.data(), depth.data());
     gpu_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (r == KFX_TRACKING_LOST) {
       std::printf("tracking fail!\n");  // kinectfusion.cpp:99
     } else if (r != KFX_OK) {
       std::fprintf(stderr, "error: %s\n", kfx_last_error());
       return 1;
+    }
+    if (rlog) {
+      kfx_icp_quality q;
+      double fitness = 0, rmse = 0;
+      if (rep.event != 3 && (kfx_frame_quality(ctx, 0, nullptr, nullptr, &q) != KFX_OK ||
+                             kfx_quality_figures(&q, &fitness, &rmse) != KFX_OK)) {
+        std::fprintf(stderr, "error: %s\n", kfx_last_error());
+        return 1;
+      }
+      std::fprintf(rlog, "%d %d %d %d %d %.9g\n", k, rep.event, rep.keyframe_added, rep.reloc.keyframe, rep.reloc.distance,
+                   fitness);
     }
     if (qlog) {  // how well the frame sits on the model it was fused into
       kfx_icp_quality q;
@@ -312,6 +344,13 @@ int main(int argc, char **argv) {
     kfx_brick_store_destroy(store);
   }
   if (qlog) std::fclose(qlog);
+  if (rlog) {
+    int64_t held = 0;
+    kfx_keyframes_count(keyframes, &held);
+    std::printf("recover: %lld keyframes\n", (long long)held);
+    std::fclose(rlog);
+    kfx_keyframes_destroy(keyframes);
+  }
   std::printf("end! %d frames, frame_count %d, %.3f ms/frame in kfx_pipeline (host frames, PCIe incl.)\n", n,
               frames, n ? 1e3 * gpu_s / n : 0.0);
   kfx_destroy(ctx);

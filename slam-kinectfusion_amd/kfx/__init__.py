@@ -15,12 +15,13 @@ import subprocess
 
 import numpy as np
 
-from .abi import (KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, IcpQuality, IcpResult, Intrinsics, Params, Pose,
+from .abi import (FERN_DTYPE, KFX_FRAME_CUR, KFX_FRAME_PREV, KFX_OK, KFX_TRACKING_LOST, Fern, FernParams, IcpQuality,
+                  IcpResult, Intrinsics, KeyframeMatch, Params, Pose, RecoverParams, RecoverReport, RelocResult,
                   default_params, fptr, i16ptr, i64ptr, u8ptr, u16ptr)
 
 __all__ = ["KinectFusion", "KfxError", "Dataset", "png_info", "png_read_bgr8", "png_read_depth", "parse_intr",
            "comm_unique_id", "pipeline_group", "slab_balance", "write_ply", "write_ply_attr", "write_ply_mesh_attr",
-           "write_ply_mesh_indexed", "write_ppm", "shift_for_pose", "quality_figures", "quality_chunk", "icp_multi_chunk", "IcpQuality", "IcpResult", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
+           "write_ply_mesh_indexed", "write_ppm", "shift_for_pose", "quality_figures", "quality_chunk", "icp_multi_chunk", "Keyframes", "fern_table", "keyframes_search_chunk", "IcpQuality", "IcpResult", "VIEW_KINDS", "VERTEX_DTYPE", "BRICK_DTYPE", "BrickStore", "lib", "build", "LIB_PATH", "Intrinsics", "Params", "Pose",
            "default_params", "KFX_FRAME_CUR", "KFX_FRAME_PREV", "KFX_OK", "KFX_TRACKING_LOST", "EXPORTS"]
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,6 +56,10 @@ EXPORTS = [
     "kfx_stage_icp_residuals", "kfx_score_poses", "kfx_frame_quality", "kfx_score_view", "kfx_get_quality_ms",
     "kfx_quality_figures", "kfx_quality_chunk",
     "kfx_icp_multi", "kfx_track_view", "kfx_resume_at", "kfx_icp_multi_chunk", "kfx_get_icp_multi_ms",
+    "kfx_fern_table", "kfx_keyframes_create", "kfx_keyframes_destroy", "kfx_keyframes_get_table", "kfx_keyframes_count",
+    "kfx_encode_frame", "kfx_keyframes_add", "kfx_keyframes_put", "kfx_keyframes_consider", "kfx_keyframes_get",
+    "kfx_keyframes_search", "kfx_keyframes_search_chunk", "kfx_keyframes_export", "kfx_keyframes_import",
+    "kfx_get_keyframe_ms", "kfx_relocalise", "kfx_pipeline_recover",
     "kfx_dataset_open", "kfx_dataset_info", "kfx_dataset_read", "kfx_dataset_close", "kfx_png_info",
     "kfx_png_read_bgr8", "kfx_png_read_depth", "kfx_parse_intr",
 ]
@@ -216,6 +221,23 @@ def lib():
         "kfx_resume_at": ([vp, P(Pose)], i),
         "kfx_icp_multi_chunk": ([i, i, C.c_int64], i),
         "kfx_get_icp_multi_ms": ([vp, P(f)], i),
+        "kfx_fern_table": ([P(Intrinsics), i, P(FernParams), vp], i),
+        "kfx_keyframes_create": ([vp, P(FernParams), vp, P(vp)], i),
+        "kfx_keyframes_destroy": ([vp], i),
+        "kfx_keyframes_get_table": ([vp, vp], i),
+        "kfx_keyframes_count": ([vp, P(C.c_int64)], i),
+        "kfx_encode_frame": ([vp, vp, P(C.c_uint64)], i),
+        "kfx_keyframes_add": ([vp, vp, P(Pose), P(C.c_int32)], i),
+        "kfx_keyframes_put": ([vp, P(Pose), P(C.c_uint64), P(C.c_int32)], i),
+        "kfx_keyframes_consider": ([vp, vp, C.c_int32, P(C.c_int32), P(KeyframeMatch)], i),
+        "kfx_keyframes_get": ([vp, C.c_int32, P(Pose), P(C.c_uint64)], i),
+        "kfx_keyframes_search": ([vp, vp, P(C.c_uint64), C.c_int64, i, vp], i),
+        "kfx_keyframes_search_chunk": ([C.c_int64, C.c_int64], i),
+        "kfx_keyframes_export": ([vp, vp, C.c_int64, P(C.c_int64)], i),
+        "kfx_keyframes_import": ([vp, vp, C.c_int64, P(vp)], i),
+        "kfx_get_keyframe_ms": ([vp, P(f)], i),
+        "kfx_relocalise": ([vp, vp, i, P(Pose), C.c_int64, C.c_double, P(RelocResult)], i),
+        "kfx_pipeline_recover": ([vp, vp, P(C.c_uint8), P(f), P(RecoverParams), P(RecoverReport)], i),
         "kfx_dataset_open": ([C.c_char_p, P(vp)], i),
         "kfx_dataset_info": ([vp, P(Intrinsics), P(i), P(i)], i),
         "kfx_dataset_read": ([vp, i, P(C.c_uint8), P(f)], i),
@@ -300,6 +322,129 @@ def icp_multi_chunk(width: int, height: int, n: int) -> int:
     """kfx_icp_multi_chunk: poses one block of an icp_multi batch of n walks at a width x height level."""
     return _check(lib().kfx_icp_multi_chunk(int(width), int(height), int(n)), "kfx_icp_multi_chunk",
                   ok=range(1, 17))
+
+
+def keyframes_search_chunk(n_keyframes: int, q: int) -> int:
+    """kfx_keyframes_search_chunk: queries one block walks in a search of q codes over n keyframes."""
+    return _check(lib().kfx_keyframes_search_chunk(int(n_keyframes), int(q)), "kfx_keyframes_search_chunk",
+                  ok=tuple(range(1, 17)))
+
+
+def _fern_params(m=512, seed=2013, depth_mm=(400, 4000)) -> FernParams:
+    return FernParams(int(m), int(depth_mm[0]), int(depth_mm[1]), int(seed))
+
+
+def fern_table(intr, pyramid_height: int = 3, m: int = 512, seed: int = 2013, depth_mm=(400, 4000)) -> np.ndarray:
+    """kfx_fern_table (host only): the generated table as a FERN_DTYPE array of m records."""
+    out = np.zeros(max(int(m), 0) if 0 <= int(m) <= 4096 else 0, FERN_DTYPE)
+    buf = np.zeros(max(out.size, 1), FERN_DTYPE)
+    I, fp = Intrinsics.from_any(intr), _fern_params(m, seed, depth_mm)
+    _check(lib().kfx_fern_table(C.byref(I), int(pyramid_height), C.byref(fp), buf.ctypes.data), "kfx_fern_table")
+    return buf[:out.size].copy()
+
+
+class Keyframes:
+    """kfx_keyframes: the device-resident keyframe store of a KinectFusion context.  Codes are
+    uint64 arrays of m / 16 words, matches (id, distance) pairs in match order."""
+
+    def __init__(self, kf: "KinectFusion", m: int = 512, seed: int = 2013, depth_mm=(400, 4000), table=None,
+                 _handle=None):
+        self.kf = kf
+        if _handle is not None:
+            self._h = _handle
+        else:
+            h = C.c_void_p()
+            t = None if table is None else np.ascontiguousarray(table, FERN_DTYPE)
+            fp = _fern_params(m if t is None else t.size, seed, depth_mm)
+            _check(lib().kfx_keyframes_create(kf._h, C.byref(fp), None if t is None else t.ctypes.data, C.byref(h)),
+                   "kfx_keyframes_create")
+            self._h = h
+        self.m = int(self.table().size)
+        self.words = self.m // 16
+
+    @staticmethod
+    def load(kf: "KinectFusion", blob: bytes) -> "Keyframes":
+        """kfx_keyframes_import."""
+        h = C.c_void_p()
+        b = np.frombuffer(bytes(blob), np.uint8)
+        _check(lib().kfx_keyframes_import(kf._h, b.ctypes.data if b.size else None, b.size, C.byref(h)),
+               "kfx_keyframes_import")
+        return Keyframes(kf, _handle=h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().kfx_keyframes_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __len__(self):
+        n = C.c_int64()
+        _check(lib().kfx_keyframes_count(self._h, C.byref(n)), "kfx_keyframes_count")
+        return int(n.value)
+
+    def table(self) -> np.ndarray:
+        probe = np.zeros(1024, FERN_DTYPE)
+        probe["x"] = -7
+        _check(lib().kfx_keyframes_get_table(self._h, probe.ctypes.data), "kfx_keyframes_get_table")
+        return probe[:int(np.count_nonzero(probe["x"] != -7))].copy()
+
+    def encode(self) -> np.ndarray:
+        code = np.zeros(self.words, np.uint64)
+        _check(lib().kfx_encode_frame(self.kf._h, self._h, code.ctypes.data_as(C.POINTER(C.c_uint64))), "kfx_encode_frame")
+        return code
+
+    def add(self, cam_pose=None) -> int:
+        P = None if cam_pose is None else (cam_pose if isinstance(cam_pose, Pose) else Pose.from_matrix(cam_pose))
+        k = C.c_int32(-1)
+        _check(lib().kfx_keyframes_add(self.kf._h, self._h, None if P is None else C.byref(P), C.byref(k)),
+               "kfx_keyframes_add")
+        return int(k.value)
+
+    def put(self, cam_pose, code) -> int:
+        P = cam_pose if isinstance(cam_pose, Pose) else Pose.from_matrix(cam_pose)
+        c = np.ascontiguousarray(code, np.uint64)
+        if c.size != self.words:
+            raise ValueError("a code has m / 16 words")
+        k = C.c_int32(-1)
+        _check(lib().kfx_keyframes_put(self._h, C.byref(P), c.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(k)),
+               "kfx_keyframes_put")
+        return int(k.value)
+
+    def consider(self, min_distance: int) -> tuple:
+        """kfx_keyframes_consider: (new id or -1, (nearest id, distance) before the add)."""
+        k, m = C.c_int32(-1), KeyframeMatch(-1, -1)
+        _check(lib().kfx_keyframes_consider(self.kf._h, self._h, int(min_distance), C.byref(k), C.byref(m)),
+               "kfx_keyframes_consider")
+        return int(k.value), (int(m.id), int(m.distance))
+
+    def get(self, k: int) -> tuple:
+        P, code = Pose(), np.zeros(self.words, np.uint64)
+        _check(lib().kfx_keyframes_get(self._h, int(k), C.byref(P), code.ctypes.data_as(C.POINTER(C.c_uint64))),
+               "kfx_keyframes_get")
+        return P, code
+
+    def search(self, codes=None, k: int = 4) -> np.ndarray:
+        """kfx_keyframes_search: (q, k, 2) int32 of (id, distance) in match order, -1 in unused slots.
+        codes: (q, m / 16) uint64, or None for the frame's own code (q = 1)."""
+        if codes is None:
+            c, q = None, 1
+        else:
+            c = np.ascontiguousarray(codes, np.uint64).reshape(-1, self.words)
+            q = c.shape[0]
+        out = np.full((max(q, 1), max(int(k), 1), 2), -9, np.int32)
+        _check(lib().kfx_keyframes_search(self.kf._h, self._h,
+                                          None if c is None or q == 0 else c.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          q, int(k), out.ctypes.data), "kfx_keyframes_search")
+        return out[:q]
+
+    def export(self) -> bytes:
+        n = C.c_int64()
+        _check(lib().kfx_keyframes_export(self._h, None, 0, C.byref(n)), "kfx_keyframes_export")
+        b = np.zeros(n.value, np.uint8)
+        _check(lib().kfx_keyframes_export(self._h, b.ctypes.data, b.size, C.byref(n)), "kfx_keyframes_export")
+        return b.tobytes()
 
 
 def shift_for_pose(params: Params, volume_pose, cam_pose, ahead_m: float) -> tuple:
@@ -905,6 +1050,35 @@ class KinectFusion:
         """kfx_resume_at: the next frame tracks from the world pose cam_pose against the volume as it stands."""
         V = cam_pose if isinstance(cam_pose, Pose) else Pose.from_matrix(cam_pose)
         _check(lib().kfx_resume_at(self._h, C.byref(V)), "kfx_resume_at")
+
+    # ---- relocalisation (DESIGN.md §28) -------------------------------------
+    def relocalise(self, keyframes: "Keyframes", k: int = 4, starts=None, min_fitness: float = 0.5) -> RelocResult:
+        """kfx_relocalise: retrieve the k nearest keyframes, track against each one's view from every start
+        (None: the identity), pick the best.  result.status is KFX_OK or KFX_TRACKING_LOST."""
+        out = RelocResult()
+        if starts is None:
+            arr, n = None, 1
+        else:
+            ps = [p if isinstance(p, Pose) else Pose.from_matrix(p) for p in starts]
+            arr, n = (Pose * max(len(ps), 1))(*ps), len(ps)
+        _check(lib().kfx_relocalise(self._h, keyframes._h, int(k), arr, n, float(min_fitness), C.byref(out)),
+               "kfx_relocalise", ok=(KFX_OK, KFX_TRACKING_LOST))
+        return out
+
+    def pipeline_recover(self, keyframes: "Keyframes", color: np.ndarray, depth: np.ndarray, params=None) -> tuple:
+        """kfx_pipeline_recover: (status, RecoverReport); params a RecoverParams or None for the defaults."""
+        color = np.ascontiguousarray(color, np.uint8)
+        d = np.ascontiguousarray(depth, np.float32)
+        rep = RecoverReport()
+        rc = lib().kfx_pipeline_recover(self._h, keyframes._h, u8ptr(color), fptr(d),
+                                        None if params is None else C.byref(params), C.byref(rep))
+        return _check(rc, "kfx_pipeline_recover", ok=(KFX_OK, KFX_TRACKING_LOST)), rep
+
+    def keyframe_ms(self) -> dict:
+        """Device ms of the last frame encode and the last keyframe search."""
+        a = (C.c_float * 2)()
+        _check(lib().kfx_get_keyframe_ms(self._h, a), "kfx_get_keyframe_ms")
+        return {"encode": float(a[0]), "search": float(a[1])}
 
     def icp_multi_ms(self) -> dict:
         """Device ms of the last icp_multi / track_view: the view raycasts, the loop, the final scoring (0: none)."""

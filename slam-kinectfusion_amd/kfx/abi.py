@@ -87,6 +87,44 @@ class IcpResult(C.Structure):
                 bytes(self.x))
 
 
+class Fern(C.Structure):
+    """kfx_fern (16 bytes): a pixel of the fern grid and its four thresholds."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("tb", C.c_uint8), ("tg", C.c_uint8), ("tr", C.c_uint8),
+                ("pad", C.c_uint8), ("td", C.c_float)]
+
+
+FERN_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("tb", "u1"), ("tg", "u1"), ("tr", "u1"), ("pad", "u1"), ("td", "<f4")])
+
+
+class FernParams(C.Structure):
+    _fields_ = [("n_ferns", C.c_int32), ("depth_min_mm", C.c_uint32), ("depth_max_mm", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class KeyframeMatch(C.Structure):
+    _fields_ = [("id", C.c_int32), ("distance", C.c_int32)]
+
+
+class RelocResult(C.Structure):
+    """kfx_reloc_result (248 bytes)."""
+    _fields_ = [("status", C.c_int32), ("keyframe", C.c_int32), ("distance", C.c_int32), ("start", C.c_int32),
+                ("n_matches", C.c_int32), ("n_converged", C.c_int32), ("world", Pose), ("icp", IcpResult),
+                ("q", IcpQuality)]
+
+    def fields(self) -> tuple:
+        """Everything as integers and bit patterns."""
+        return (int(self.status), int(self.keyframe), int(self.distance), int(self.start), int(self.n_matches),
+                int(self.n_converged), bytes(self.world), self.icp.fields(), self.q.fields())
+
+
+class RecoverParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("harvest_min_distance", C.c_int32), ("min_fitness", C.c_double),
+                ("harvest_min_fitness", C.c_double)]
+
+
+class RecoverReport(C.Structure):
+    _fields_ = [("event", C.c_int32), ("keyframe_added", C.c_int32), ("reloc", RelocResult)]
+
+
 def default_params(dims: int = 512, range_m: float = 3.0) -> Params:
     """kinectfuison_params::default_params (kinectfusion.cpp:167-190), with the
     volume size/range overridable (BASELINE configs use 4 mm / 2 mm voxels)."""
