@@ -281,21 +281,15 @@ int save_indexed(const char *path, const char *call, Extract extract) {
   return kfx_write_ply_mesh_indexed(path, v.data(), nv, t.data(), nt);
 }
 
-}  // namespace
-
-extern "C" {
-
-// ---- free-viewpoint render (DESIGN.md §18) --------------------------------
-
 // Affine3f product and rigid inverse in the float order of the device's
 // pose_mul / pose_inv (k_ray_pose; the oracle's kfo_pose_mul / kfo_pose_inv):
 // this file is built without contraction, so the host sums round the same.
-static DevPose host_pose_mul(const DevPose &a, const DevPose &b) {
+DevPose host_pose_mul(const DevPose &a, const DevPose &b) {
   DevPose r;
   pose_mul_f32(a.R, a.t, b.R, b.t, r.R, r.t);  // (kfx_multi.h: the same loops, where a host check can build them)
   return r;
 }
-static DevPose host_pose_inv(const DevPose &a) {
+DevPose host_pose_inv(const DevPose &a) {
   DevPose r;
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) r.R[3 * i + j] = a.R[3 * j + i];
@@ -307,12 +301,60 @@ static DevPose host_pose_inv(const DevPose &a) {
   return r;
 }
 
+// What the two view calls do once their own refusals are past: reserve the
+// staging buffers (`who` names the call in an out-of-memory message), place the
+// optional maps in view_maps as [vmap | nmap | ts], compose cam2vol =
+// box_pose^-1 * cam_pose (tsdf_volume.cpp:59), launch(g, cam2vol, eye, vmap,
+// nmap, ts) between the two events ev, copy out what was asked
+// for and leave the launch's device time in *ms.  On the frame stream, behind
+// every queued frame's integrate; nothing the tracker reads is written, and
+// the pending tracking status is left alone.
+template <class Launch>
+int view_run(kfx_ctx *c, const char *who, hipEvent_t *ev, float *ms, const DevPose &box_pose,
+             const kfx_intrinsics *view, const kfx_pose *cam_pose, uint8_t *out, float *vmap, float *nmap, float *ts,
+             Launch launch) {
+  int r;
+  const size_t np = (size_t)view->width * view->height;
+  const bool maps = vmap || nmap || ts;
+  if ((r = reserve((void **)&c->view_out, &c->view_out_cap, 3 * np, who))) return r;
+  if (maps && (r = reserve((void **)&c->view_maps, &c->view_maps_cap, 28 * np, who))) return r;
+  if ((r = make_events(ev, 2))) return r;
+  float *dv = vmap ? c->view_maps : nullptr, *dn = nmap ? c->view_maps + 3 * np : nullptr,
+        *dt = ts ? c->view_maps + 6 * np : nullptr;
+  const DevPose cam = to_dev(*cam_pose);
+  const DevPose c2v = host_pose_mul(host_pose_inv(box_pose), cam);
+  const LevelGeom g = {view->width, view->height, view->fx, view->fy, view->cx, view->cy};
+  HIPCHK(hipEventRecord(ev[0], c->stream));
+  launch(g, c2v, cam.t, dv, dn, dt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev[1], c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->view_out, 3 * np, hipMemcpyDeviceToHost, c->stream));
+  if (vmap) HIPCHK(hipMemcpyAsync(vmap, dv, 12 * np, hipMemcpyDeviceToHost, c->stream));
+  if (nmap) HIPCHK(hipMemcpyAsync(nmap, dn, 12 * np, hipMemcpyDeviceToHost, c->stream));
+  if (ts) HIPCHK(hipMemcpyAsync(ts, dt, 4 * np, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(ms, ev[0], ev[1]));
+  return KFX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- free-viewpoint render (DESIGN.md §18) --------------------------------
+
+// a view's size (kfx_save_world_view checks it before anything else: null is a bad size there)
+static int view_size(const kfx_intrinsics *view) {
+  if (!view || view->width < 1 || view->height < 1 || (int64_t)view->width * view->height > ((int64_t)1 << 26))
+    return set_err(KFX_ERR_ARG, "view size: width, height >= 1 and width * height <= 2^26");
+  return KFX_OK;
+}
+
 // the argument checks kfx_render_view and kfx_world_view share
 static int view_args(const kfx_intrinsics *view, const kfx_pose *cam_pose, const uint8_t *out, int type) {
   if (!view || !cam_pose || !out) return set_err(KFX_ERR_ARG, "null argument");
   if (type < KFX_VIEW_PHONG || type > KFX_VIEW_COLOR) return set_err(KFX_ERR_ARG, "view type outside 0..2");
-  if (view->width < 1 || view->height < 1 || (int64_t)view->width * view->height > ((int64_t)1 << 26))
-    return set_err(KFX_ERR_ARG, "view size: width, height >= 1 and width * height <= 2^26");
+  if (int r = view_size(view)) return r;
   if (!std::isfinite(view->fx) || !std::isfinite(view->fy) || view->fx == 0.f || view->fy == 0.f ||
       !std::isfinite(view->cx) || !std::isfinite(view->cy))
     return set_err(KFX_ERR_ARG, "view intrinsics: finite, fx and fy non-zero");
@@ -327,29 +369,10 @@ int kfx_render_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_
   if (r) return r;
   if ((r = view_args(view, cam_pose, out, type))) return r;
   if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "render_view on one slab of several");
-  const size_t np = (size_t)view->width * view->height;
-  const bool maps = vmap || nmap || ts;
-  if ((r = reserve((void **)&c->view_out, &c->view_out_cap, 3 * np, "render_view"))) return r;
-  if (maps && (r = reserve((void **)&c->view_maps, &c->view_maps_cap, 28 * np, "render_view"))) return r;
-  if ((r = make_events(c->ev_view, 2))) return r;
-  float *dv = vmap ? c->view_maps : nullptr, *dn = nmap ? c->view_maps + 3 * np : nullptr,
-        *dt = ts ? c->view_maps + 6 * np : nullptr;
-  const DevPose cam = to_dev(*cam_pose);
-  const DevPose c2v = host_pose_mul(host_pose_inv(to_dev(c->p.volu_pose)), cam);  // tsdf_volume.cpp:59
-  const LevelGeom g = {view->width, view->height, view->fx, view->fy, view->cx, view->cy};
-  // on the frame stream, behind every queued frame's integrate; nothing the
-  // tracker reads is written, and the pending tracking status is left alone
-  HIPCHK(hipEventRecord(c->ev_view[0], c->stream));
-  launch_view(c->stream, c->vol, g, c2v, cam.t, type, c->view_out, dv, dn, dt);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_view[1], c->stream));
-  HIPCHK(hipMemcpyAsync(out, c->view_out, 3 * np, hipMemcpyDeviceToHost, c->stream));
-  if (vmap) HIPCHK(hipMemcpyAsync(vmap, dv, 12 * np, hipMemcpyDeviceToHost, c->stream));
-  if (nmap) HIPCHK(hipMemcpyAsync(nmap, dn, 12 * np, hipMemcpyDeviceToHost, c->stream));
-  if (ts) HIPCHK(hipMemcpyAsync(ts, dt, 4 * np, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipEventElapsedTime(&c->view_ms, c->ev_view[0], c->ev_view[1]));
-  return KFX_OK;
+  return view_run(c, "render_view", c->ev_view, &c->view_ms, to_dev(c->p.volu_pose), view, cam_pose, out, vmap, nmap,
+                  ts, [&](const LevelGeom &g, const DevPose &c2v, const float *eye, float *dv, float *dn, float *dt) {
+                    launch_view(c->stream, c->vol, g, c2v, eye, type, c->view_out, dv, dn, dt);
+                  });
 }
 
 int kfx_get_view_ms(kfx_ctx *c, float *ms) {
@@ -1181,31 +1204,14 @@ int kfx_world_view(kfx_ctx *c, const kfx_intrinsics *view, const kfx_pose *cam_p
   if ((r = view_args(view, cam_pose, out, type))) return r;
   if (c->slab && c->world > 1) return set_err(KFX_ERR_STATE, "world_view on one slab of several");
   if (c->wv_n == 0) return set_err(KFX_ERR_STATE, "world_view: no world is loaded (kfx_world_view_load)");
-  const size_t np = (size_t)view->width * view->height;
-  const bool maps = vmap || nmap || ts;
-  if ((r = reserve((void **)&c->view_out, &c->view_out_cap, 3 * np, "world_view"))) return r;
-  if (maps && (r = reserve((void **)&c->view_maps, &c->view_maps_cap, 28 * np, "world_view"))) return r;
-  if ((r = make_events(c->ev_wv, 4))) return r;
-  float *dv = vmap ? c->view_maps : nullptr, *dn = nmap ? c->view_maps + 3 * np : nullptr,
-        *dt = ts ? c->view_maps + 6 * np : nullptr;
-  const DevPose cam = to_dev(*cam_pose);
-  const DevPose c2v = host_pose_mul(host_pose_inv(c->wv_pose), cam);
-  const LevelGeom g = {view->width, view->height, view->fx, view->fy, view->cx, view->cy};
   VolView v = c->wv_vol;
   v.force64 = c->vol.force64;
   const WorldGrid wg = {c->wv_buf[0], (uint32_t *)c->wv_buf[1], c->wv_n, c->wv_cells};
-  // on the frame stream; it reads the loaded world only and writes the view's buffers
-  HIPCHK(hipEventRecord(c->ev_wv[2], c->stream));
-  launch_world_view(c->stream, v, wg, g, c2v, cam.t, type, c->view_out, dv, dn, dt);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_wv[3], c->stream));
-  HIPCHK(hipMemcpyAsync(out, c->view_out, 3 * np, hipMemcpyDeviceToHost, c->stream));
-  if (vmap) HIPCHK(hipMemcpyAsync(vmap, dv, 12 * np, hipMemcpyDeviceToHost, c->stream));
-  if (nmap) HIPCHK(hipMemcpyAsync(nmap, dn, 12 * np, hipMemcpyDeviceToHost, c->stream));
-  if (ts) HIPCHK(hipMemcpyAsync(ts, dt, 4 * np, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipEventElapsedTime(&c->wv_ms[1], c->ev_wv[2], c->ev_wv[3]));
-  return KFX_OK;
+  // it reads the loaded world only; ev_wv[0..1] are the load's
+  return view_run(c, "world_view", c->ev_wv + 2, &c->wv_ms[1], c->wv_pose, view, cam_pose, out, vmap, nmap, ts,
+                  [&](const LevelGeom &g, const DevPose &c2v, const float *eye, float *dv, float *dn, float *dt) {
+                    launch_world_view(c->stream, v, wg, g, c2v, eye, type, c->view_out, dv, dn, dt);
+                  });
 }
 
 int kfx_get_world_view_ms(kfx_ctx *c, float out_ms[2]) {
@@ -1220,11 +1226,10 @@ int kfx_get_world_view_ms(kfx_ctx *c, float out_ms[2]) {
 int kfx_save_world_view(kfx_ctx *c, const kfx_brick_store *store, const kfx_intrinsics *view, const kfx_pose *cam_pose,
                         int type, const char *path) {
   if (!path) return set_err(KFX_ERR_ARG, "null path");
-  if (!view || view->width < 1 || view->height < 1 || (int64_t)view->width * view->height > ((int64_t)1 << 26))
-    return set_err(KFX_ERR_ARG, "view size: width, height >= 1 and width * height <= 2^26");
-  int64_t nb = 0;
-  int r = kfx_world_bricks(c, store, nullptr, 0, &nb);
+  int r = view_size(view);
   if (r) return r;
+  int64_t nb = 0;
+  if ((r = kfx_world_bricks(c, store, nullptr, 0, &nb))) return r;
   std::vector<kfx_brick> bricks;
   std::vector<uint8_t> img;
   try {

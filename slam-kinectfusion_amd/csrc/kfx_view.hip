@@ -4,66 +4,14 @@
 // or normal colours, or the fused colour) and stored as uchar3.  One launch
 // per view; it reads the volume and its occupancy maps and writes only the
 // view's own buffers.
-#include <algorithm>
-#include <climits>
-#include <cmath>
-
-#include "kfx_internal.h"
-#include "kfx_device.h"
-#include "kfx_ffadd.h"
-#include "kfx_ray.h"
-#include "kfx_raystep.h"
+#include "kfx_view_march.h"
 
 namespace kfx {
 namespace {
 
-struct ViewArgs {
-  LevelGeom g;     // the view's intrinsics
-  DevPose c2v;     // cam2vol = volume_pose^-1 * cam_pose (Rinv = its R transposed)
-  float eye[3];    // cam_pose.t: the Phong shader's eye
-  int type;        // KFX_VIEW_*
-  uint8_t *out;    // w * h uchar3
-  float *vmap, *nmap, *ts;  // optional (null: not stored)
-};
-
-// kernel_renderPhong / kernel_renderNormals on one pixel's maps: k_render's
-// arithmetic (kfx_extract.hip) with the eye passed in.  Packed c0 | c1 << 8 | c2 << 16.
-__device__ __forceinline__ unsigned shade_normal(f3 nv) {
-  return (unsigned)render_u8(fabsf(nv.x) * 255) | ((unsigned)render_u8(fabsf(nv.y) * 255) << 8) |
-         ((unsigned)render_u8(fabsf(nv.z) * 255) << 16);
-}
-__device__ __forceinline__ unsigned shade_phong(f3 nv, f3 vv, f3 eye) {
-  if ((nv.x == 0 && nv.y == 0 && nv.z == 0) || (vv.x == 0 && vv.y == 0 && vv.z == 0)) return 0u;
-  const f3 kd = {0.3843f, 0.4745f, 0.580f};
-  const float intensity = 0.9f;
-  const f3 e = normalized_ieee(sub(eye, vv));
-  const f3 l = normalized_ieee(sub({500.f, 500.f, -500.f}, vv));
-  float lc = dot(nv, l);
-  if (lc <= 0) lc = -lc;
-  float coef = intensity * lc;
-  const f3 diffuse = scl(kd, coef);
-  const f3 hv = normalized_ieee(add(l, e));
-  float hc = dot(nv, hv);
-  if (hc < 0) hc = -hc;
-  const float h2 = hc * hc, h4 = h2 * h2, h8 = h4 * h4;
-  coef = intensity * (h8 * h2);
-  const double spec = 0.5 * (double)coef;
-  const unsigned o0 = render_u8((float)fmin(1.0, (double)(0.1f + diffuse.x) + spec) * 255);
-  const unsigned o1 = render_u8((float)fmin(1.0, (double)(0.1f + diffuse.y) + spec) * 255);
-  const unsigned o2 = render_u8((float)fmin(1.0, (double)(0.1f + diffuse.z) + spec) * 255);
-  return o0 | (o1 << 8) | (o2 << 16);
-}
-
-// The fused colour at volume position P: trilinear blend of
-// the coloured corners in 8-bit fixed-point weights, all in integers.  Returns
-// false when no corner counts (outside the volume, or never coloured: packed
-// 24-bit colour 0).
-__device__ __forceinline__ bool fused_colour(const VolView &v, const RayConsts &rc, f3 P, unsigned &pix) {
-  const f3 cf = mulc(P, rc.vs_inv);
-  const int gx = f2i_rd(cf.x), gy = f2i_rd(cf.y), gz = f2i_rd(cf.z);
-  const int qx = (int)((cf.x - (float)gx) * 256.f), qy = (int)((cf.y - (float)gy) * 256.f),
-            qz = (int)((cf.z - (float)gz) * 256.f);
-  uint32_t c[8];
+// The window's colour corners for fused_colour (kfx_view_march.h): a corner
+// counts if it lies in the volume and on this slab.
+__device__ __forceinline__ void window_corners(const VolView &v, int gx, int gy, int gz, uint32_t (&c)[8]) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) {  // the 8 gathers back to back
     const int x = gx + (k >> 2), y = gy + ((k >> 1) & 1), z = gz + (k & 1);
@@ -71,61 +19,38 @@ __device__ __forceinline__ bool fused_colour(const VolView &v, const RayConsts &
                     (unsigned)(z - v.zb) < (unsigned)v.zn;
     c[k] = in ? (v.rgb[vox_index(v, x, y, z)] & 0xFFFFFFu) : 0u;
   }
-  unsigned sw = 0u, s0 = 0u, s1 = 0u, s2 = 0u;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const unsigned wx = (k >> 2) ? qx : 256 - qx, wy = ((k >> 1) & 1) ? qy : 256 - qy, wz = (k & 1) ? qz : 256 - qz;
-    const unsigned W = c[k] ? wx * wy * wz : 0u;
-    sw += W;
-    s0 += W * (c[k] & 0xFFu);
-    s1 += W * ((c[k] >> 8) & 0xFFu);
-    s2 += W * ((c[k] >> 16) & 0xFFu);
-  }
-  if (sw == 0u) return false;
-  const unsigned h = sw >> 1;
-  pix = ((s0 + h) / sw) | (((s1 + h) / sw) << 8) | (((s2 + h) / sw) << 16);
-  return true;
 }
-
-// A candidate sample's ray_len: n adds of step to L0, exactly (kfx_ffadd.h).
-// Out of line, once per normal pass: inlined, the loop's temporaries spill
-// k_view<true> at 5 waves per SIMD (68 bytes of scratch per lane).  The view's
-// own copy, so that this file adds no second body of kfx::ff_add_call.
-__device__ __attribute__((noinline)) float view_ray_len(float L0, float step, int n) { return ff_add(L0, step, n); }
 
 // A wave is an 8x8 pixel tile, a block 16x16 (k_raycast's shape: XCD-banded
 // tile order, the same march: sample-index bound, batches of kR samples,
 // empty-space skip over bocc / socc, one normal pass per wave with the
 // two-trip normal).  The pose and intrinsics are kernel arguments (scalar
 // loads); no DevState, no resize, no slab code, no block barrier.
+//
+// Set-up, shading, blend and store are kfx_view_march.h's pieces.  The loop in
+// between is view_march's, written out here over the window: under the shared
+// function this kernel, at 5 waves per SIMD, loses to its parent (DESIGN.md
+// §18).  Any change to the loop goes into view_march as well.  What the window
+// does differently from the brick grid on purpose: one round trip per batch;
+// the __all(interior) fast path only with 32-bit indices (kIdx32); the edge
+// path masks pm / nm with the sample's validity; the slab checks apply (zb / zn
+// in voxel2tsdf, tri32_ok, the colour corners' test).
 template <bool kIdx32>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kIdx32 ? KFX_RAY_OCC : KFX_RAY_SLAB_OCC)))
 void k_view(VolView v, ViewArgs a, RayConsts rc) {
   const LevelGeom g = a.g;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int nbx = (g.w + 15) / 16;
-  const int t = xcd_remap(blockIdx.x, gridDim.x);
-  const int tx0 = (t % nbx) * 16 + (wv & 1) * 8, ty0 = (t / nbx) * 16 + (wv >> 1) * 8;  // the wave's tile
-  const int x = tx0 + (lane & 7), y = ty0 + (lane >> 3);
-  const bool inimg = x < g.w && y < g.h;
-  const size_t o = (size_t)y * g.w + x;
+  const ViewPix px = view_pix(g);
+  const int lane = px.lane, tx0 = px.tx0, ty0 = px.ty0;
+  const bool inimg = px.inimg;
+  const size_t o = px.o;
   f3 vout = {0.f, 0.f, 0.f}, nout = {0.f, 0.f, 0.f}, hvert = {0.f, 0.f, 0.f};
   float hts = 0.f;
   bool hit = false;
   {
-    const f3 org = {a.c2v.t[0], a.c2v.t[1], a.c2v.t[2]};
-    float da[3];
-    ray_dir(a.c2v.R, g, x, y, da);
-    const f3 dir = {da[0], da[1], da[2]};
-    const f3 invR = {1.f / dir.x, 1.f / dir.y, 1.f / dir.z};
-    const f3 tbot = mulc(invR, sub({0.f, 0.f, 0.f}, org));
-    const f3 ttop = mulc(invR, sub({v.range[0], v.range[1], v.range[2]}, org));
-    const f3 tmin = {fminf(ttop.x, tbot.x), fminf(ttop.y, tbot.y), fminf(ttop.z, tbot.z)};
-    const f3 tmax = {fmaxf(ttop.x, tbot.x), fmaxf(ttop.y, tbot.y), fmaxf(ttop.z, tbot.z)};
-    const float tnear = fmaxf(fmaxf(tmin.x, tmin.y), fmaxf(tmin.x, tmin.z));
-    const float tfar = fminf(fminf(tmax.x, tmax.y), fminf(tmax.x, tmax.z));
-    const float ray0 = fmaxf(tnear, 0.f);
-    bool live = inimg && ray0 < tfar;
+    const ViewRay ray = view_ray(a.c2v, g, v, px);
+    const f3 org = ray.org, dir = ray.dir;
+    const float tfar = ray.tfar, ray0 = ray.ray0;
+    bool live = ray.live;
     const f3 vstep = mulc(dir, rc.vs);
     // samples 1 .. kend - 1 of the reference's loop (kfx_raystep.h); a hit
     // candidate's ray_len is ff_add(L0, step, k - 1)
@@ -293,7 +218,7 @@ void k_view(VolView v, ViewArgs a, RayConsts rc) {
     const f3 eye = {a.eye[0], a.eye[1], a.eye[2]};
     if (a.type == 1) {
       pix = shade_normal(nout);
-    } else if (a.type == 0 || !fused_colour(v, rc, hvert, pix)) {
+    } else if (a.type == 0 || !fused_colour(rc, hvert, pix, [&](int gx, int gy, int gz, uint32_t (&c)[8]) { window_corners(v, gx, gy, gz, c); })) {
       // colour: only hit lanes gather, after the normal was accepted; a hit
       // with no coloured corner keeps its Phong value
       pix = shade_phong(nout, vout, eye);
@@ -304,39 +229,7 @@ void k_view(VolView v, ViewArgs a, RayConsts rc) {
     if (a.nmap) st3(a.nmap, o, nout);
     if (a.ts) a.ts[o] = hts;
   }
-  // Store: a tile row is 8 pixels = 24 bytes of one image row.  Lane (r, k) =
-  // (lane >> 3, lane & 7) assembles the aligned dword k of row r's segment
-  // from the row's packed pixels with four lane reads (ds_bpermute: no LDS
-  // allocation, no barrier) and stores it whole; only a dword that hangs over
-  // an end of the segment (an unaligned row start, the image's right edge)
-  // is stored as its bytes.  Rows below the image and dwords outside the
-  // segment store nothing.
-  {
-    const int r = lane >> 3, k = lane & 7;
-    const int ry = ty0 + r;
-    const int nb = (ry < g.h && tx0 < g.w) ? 3 * min(8, g.w - tx0) : 0;  // bytes of the row segment
-    const size_t gb = ((size_t)ry * g.w + tx0) * 3;                      // its first byte in the image
-    const int head = (int)(gb & 3);
-    unsigned word = 0u, okm = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int rb = 4 * k - head + j;  // byte of the row segment
-      const bool ok = rb >= 0 && rb < nb;
-      const int rc3 = ok ? rb : 0;
-      const int px = rc3 / 3, ch = rc3 - 3 * px;
-      const unsigned p = (unsigned)__shfl((int)pix, (r << 3) | px);
-      word |= ((p >> (8 * ch)) & 0xFFu) << (8 * j);
-      okm |= ok ? (1u << j) : 0u;
-    }
-    uint8_t *dst = a.out + (gb - head) + 4 * (size_t)k;
-    if (okm == 0xFu) {
-      *reinterpret_cast<uint32_t *>(dst) = word;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if ((okm >> j) & 1u) dst[j] = (uint8_t)(word >> (8 * j));
-    }
-  }
+  view_store(a.out, g, tx0, ty0, lane, pix);
 }
 
 }  // namespace
@@ -344,22 +237,8 @@ void k_view(VolView v, ViewArgs a, RayConsts rc) {
 void launch_view(hipStream_t s, VolView v, LevelGeom g, DevPose cam2vol, const float eye[3], int type, uint8_t *out,
                  float *vmap, float *nmap, float *ts) {
   RayConsts rc;
-  rc.vs = {v.vs[0], v.vs[1], v.vs[2]};
-  rc.vs_inv = {1.f / v.vs[0], 1.f / v.vs[1], 1.f / v.vs[2]};
-  rc.gd = {v.vs[0] * 0.5f, v.vs[1] * 0.5f, v.vs[2] * 0.5f};
-  rc.step = v.vs[0];
-  // half an ulp of a position inside the volume is <= max_dim * 2^-23 voxels
-  rc.skip_cap = std::min(511.f, std::floor(0.1f * 8388608.f / (float)std::max(v.X, std::max(v.Y, v.Z))));
-  ViewArgs a{};
-  a.g = g;
-  a.c2v = cam2vol;
-  for (int i = 0; i < 3; ++i) a.eye[i] = eye[i];
-  a.type = type;
-  a.out = out;
-  a.vmap = vmap;
-  a.nmap = nmap;
-  a.ts = ts;
-  const dim3 grd(((g.w + 15) / 16) * ((g.h + 15) / 16));
+  ViewArgs a;
+  const dim3 grd = view_fill(v, g, cam2vol, eye, type, out, vmap, nmap, ts, rc, a);
   // 32-bit tsdf byte offsets (24-bit operands of the tile * zn products), as launch_raycast
   const bool idx32 = !v.force64 && v.local_voxels() < (1ull << 31) && (size_t)v.tiles_x * v.tiles_y < (1ull << 24) &&
                      v.zn < (1 << 24);

@@ -954,13 +954,7 @@ class KinectFusion:
                "kfx_render")
         return out
 
-    def render_view(self, intr, pose, kind: str = "phong", maps: bool = False):
-        """kfx_render_view: the volume as it stands seen from camera-to-world
-        `pose` (4x4 matrix or Pose) through `intr` (any size and focal lengths);
-        kind "phong", "normal" or "color" (the fused colour, BGR).  Returns the
-        (H, W, 3) uint8 image, with maps=True (image, vmap, nmap, ts): the
-        view's (H, W, 3) float32 vertex and normal maps and the (H, W) float32
-        distance along each ray (0: no surface).  Tracking state is untouched."""
+    def _view(self, name: str, intr, pose, kind: str, maps: bool):
         I = Intrinsics.from_any(intr)
         P = pose if isinstance(pose, Pose) else Pose.from_matrix(pose)
         h, w = max(I.height, 0), max(I.width, 0)
@@ -968,10 +962,19 @@ class KinectFusion:
         vm = np.zeros((h, w, 3), np.float32) if maps else None
         nm = np.zeros((h, w, 3), np.float32) if maps else None
         ts = np.zeros((h, w), np.float32) if maps else None
-        _check(lib().kfx_render_view(self._h, C.byref(I), C.byref(P), VIEW_KINDS[kind],
-                                     out.ctypes.data_as(C.POINTER(C.c_uint8)), fptr(vm) if maps else None,
-                                     fptr(nm) if maps else None, fptr(ts) if maps else None), "kfx_render_view")
+        _check(getattr(lib(), name)(self._h, C.byref(I), C.byref(P), VIEW_KINDS[kind],
+                                    out.ctypes.data_as(C.POINTER(C.c_uint8)), fptr(vm) if maps else None,
+                                    fptr(nm) if maps else None, fptr(ts) if maps else None), name)
         return (out, vm, nm, ts) if maps else out
+
+    def render_view(self, intr, pose, kind: str = "phong", maps: bool = False):
+        """kfx_render_view: the volume as it stands seen from camera-to-world
+        `pose` (4x4 matrix or Pose) through `intr` (any size and focal lengths);
+        kind "phong", "normal" or "color" (the fused colour, BGR).  Returns the
+        (H, W, 3) uint8 image, with maps=True (image, vmap, nmap, ts): the
+        view's (H, W, 3) float32 vertex and normal maps and the (H, W) float32
+        distance along each ray (0: no surface).  Tracking state is untouched."""
+        return self._view("kfx_render_view", intr, pose, kind, maps)
 
     def view_ms(self) -> float:
         """Device milliseconds of the last render_view launch (HIP events)."""
@@ -1231,17 +1234,7 @@ class KinectFusion:
 
     def world_view(self, intr, pose, kind: str = "phong", maps: bool = False):
         """kfx_world_view: render_view of the loaded world (same arguments, same return shapes)."""
-        I = Intrinsics.from_any(intr)
-        P = pose if isinstance(pose, Pose) else Pose.from_matrix(pose)
-        h, w = max(I.height, 0), max(I.width, 0)
-        out = np.zeros((h, w, 3), np.uint8)
-        vm = np.zeros((h, w, 3), np.float32) if maps else None
-        nm = np.zeros((h, w, 3), np.float32) if maps else None
-        ts = np.zeros((h, w), np.float32) if maps else None
-        _check(lib().kfx_world_view(self._h, C.byref(I), C.byref(P), VIEW_KINDS[kind],
-                                    out.ctypes.data_as(C.POINTER(C.c_uint8)), fptr(vm) if maps else None,
-                                    fptr(nm) if maps else None, fptr(ts) if maps else None), "kfx_world_view")
-        return (out, vm, nm, ts) if maps else out
+        return self._view("kfx_world_view", intr, pose, kind, maps)
 
     def world_view_ms(self) -> dict:
         """Device ms of the last world_view_load (without the upload) and the last world_view (HIP events)."""
